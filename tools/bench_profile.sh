@@ -5,11 +5,11 @@
 OUT=$1; shift
 ARGS=("$@")
 mkdir -p "$OUT"
-timeout -k 10 400 python -u bench.py "${ARGS[@]}" > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 400 python -u bench.py --full "${ARGS[@]}" > "$OUT/bench.json" 2> "$OUT/bench.err"
 echo "bench rc=$?"
 cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd /root/repo
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run -f csv -- python -u bench.py "${ARGS[@]}" --no-cpu-baseline --steps 3 --warmup 1 > "$OUT/trace.log" 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run -f csv -- python -u bench.py --full "${ARGS[@]}" --no-cpu-baseline --steps 3 --warmup 1 > "$OUT/trace.log" 2>&1
 echo "trace rc=$?"
 # (DTGPU_PASS_MARK: every pass opens with a marker kernel, so tools/traffic.py sums exactly the
 # last pass; --no-decode --no-encode: nothing runs after it)

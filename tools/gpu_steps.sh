@@ -54,11 +54,11 @@ for s in ${STEPS//,/ }; do
     pmc)
       bash tools/pmc.sh "$OUT/pmc" python -u tools/kbench.py friendsforever 10000 1; ok pmc $? ;;
     mixed)
-      timeout -k 10 300 python -u bench.py --workload mixed --docs 400 --steps 3 --warmup 1 --no-cpu-baseline \
+      timeout -k 10 300 python -u bench.py --full --workload mixed --docs 400 --steps 3 --warmup 1 --no-cpu-baseline \
         > "$OUT/mixed.json" 2> "$OUT/mixed.err"
       rc=$?; head -c 400 "$OUT/mixed.json"; echo; ok mixed $rc ;;
     synth)
-      timeout -k 10 900 python -u bench.py --workload synth --distinct ${SYNTH_DISTINCT:-1024} \
+      timeout -k 10 900 python -u bench.py --full --workload synth --distinct ${SYNTH_DISTINCT:-1024} \
         --docs ${SYNTH_DOCS:-20000} --steps 3 --warmup 1 --no-cpu-baseline > "$OUT/synth.json" 2> "$OUT/synth.err"
       rc=$?; head -c 400 "$OUT/synth.json"; echo; tail -3 "$OUT/synth.err"; ok synth $rc ;;
     level)
