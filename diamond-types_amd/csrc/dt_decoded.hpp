@@ -1,6 +1,6 @@
 // dt_decoded.hpp -- the decoder handle (dtgpu_decoded): device arenas of a decoded batch,
 // shared by the decode API (dtgpu_decode.cpp) and the device-staged checkout batches
-// (dtgpu_api.cpp), which read the decoded oplogs in place.
+// (dtgpu_stage.cpp), which read the decoded oplogs in place.
 #pragma once
 #include <hip/hip_runtime.h>
 

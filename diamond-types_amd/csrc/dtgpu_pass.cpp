@@ -1,0 +1,538 @@
+// dtgpu_pass.cpp -- checkout passes over a staged batch (dtgpu_stage.cpp): what one pass enqueues,
+// the dtgpu_batch_run* entry points, the batched encoder, and the batch's read-back accessors.
+#include <cstdio>
+#include <cstring>
+
+#include "dt_batch.hpp"
+
+using namespace dtgpu;
+
+namespace {
+
+int replay_all(dtgpu_batch *B, hipStream_t s, int skip_tier = -1) {
+    ReplayLaunch r{};
+    BatchParams tiers[kLdsTiers];
+    for (int t = 0; t < kLdsTiers; t++) {
+        tiers[t] = B->tier[t];
+        if (t == skip_tier) tiers[t].n_list = 0;   // replayed by the split pipeline
+    }
+    r.lds = tiers;
+    r.keep_fb = skip_tier >= 0;
+    r.join_side = skip_tier >= 0 ? kLdsTiers - 1 - skip_tier : -1;   // launch_split_side's stream
+    r.n_lds = kLdsTiers;
+    r.large = &B->large;
+    r.stream = s;
+    for (int k = 0; k < kSideStreams; k++) { r.side[k] = B->side[k]; r.ev_join[k] = B->ev_join[k]; }
+    r.ev_fork = B->ev_fork;
+    // split pass: a segment of a big-tier document may sit in a tier replayed from s
+    if (skip_tier >= 0 && !B->seg_groups.empty() && hipStreamWaitEvent(s, B->ev_splan, 0) != hipSuccess) return ErrHip;
+    const int e = launch_replay(r);
+    return e ? e : launch_combine(B->comb, s);   // cut documents: their segments' texts joined
+}
+// A split pass plans its cuts beside the side pipeline's prep, before the main pipeline's: the cut
+// kernel then finds each parent's entry itself.
+CutParams cut_before_prep(const dtgpu_batch *B) {
+    CutParams c = B->cut;
+    c.pent = nullptr;
+    return c;
+}
+// The split pass's side pipeline (see stage_device): after a fork from s, the big tier's
+// prep, plan and replay on its side stream.  The fallback counter is reset first, on s, since
+// both pipelines' LDS tiers append to it; the main pipeline's replay_all(skip_tier) joins the
+// side stream (launch_replay's fork / join of that tier's stream) before the HBM tier.
+int launch_split_side(dtgpu_batch *B, hipStream_t s) {
+    const int tb = B->split_tier;
+    hipStream_t sb = B->side[kLdsTiers - 1 - tb];
+    const BatchParams &q = B->tier[tb];
+    if (q.fb_count && hipMemsetAsync(const_cast<uint32_t *>(q.fb_count), 0, sizeof(uint32_t), s) != hipSuccess) return ErrHip;
+    if (hipEventRecord(B->ev_fork, s) != hipSuccess || hipStreamWaitEvent(sb, B->ev_fork, 0) != hipSuccess) return ErrHip;
+    PrepParams pp = B->prep;
+    pp.doc_list = B->d_split.p;
+    pp.n_docs = B->n_big;
+    PlanParams qq = B->plan;
+    qq.doc_list = B->d_split.p;
+    qq.n_docs = B->n_big;
+    // as prep_and_plan: the walk (CSR mode, after prep's first half) on a stream of its own,
+    // beside the chain decomposition and prep's second half
+    const bool overlap = B->n_gpu_planned && B->prep.chain_flag && !B->prep.check && B->plan.walk && B->plan.coff &&
+                         B->ws_side && B->cfg.walk_overlap;
+    if (overlap) {
+        pp.short_rec = B->plan.split ? 1u : 0u;
+        if (launch_prep_stage(pp, sb, 1)) return ErrHip;
+        if (hipEventRecord(B->ev_sw0, sb) != hipSuccess || hipStreamWaitEvent(B->ws_side, B->ev_sw0, 0) != hipSuccess) return ErrHip;
+        if (launch_walk(qq, B->ws_side, true) != OK || hipEventRecord(B->ev_sw1, B->ws_side) != hipSuccess) return ErrHip;
+        if (launch_prep_stage(pp, sb, 2) || launch_prep_stage(pp, sb, 3)) return ErrHip;
+        if (hipStreamWaitEvent(sb, B->ev_sw1, 0) != hipSuccess || launch_plan(qq, sb, false) != OK) return ErrHip;
+    } else {
+        if (launch_prep(pp, sb)) return ErrHip;
+        if (B->n_gpu_planned && launch_plan(qq, sb) != OK) return ErrHip;
+    }
+    if (hipEventRecord(B->ev_splan, sb) != hipSuccess) return ErrHip;
+    // the cut planning on s, beside the side pipeline's prep and plan (the main pipeline's prep
+    // follows it there); the side replay waits for it
+    if (B->cut.n_groups && (launch_cut(cut_before_prep(B), s) || hipEventRecord(B->ev_cut, s) != hipSuccess ||
+                            hipStreamWaitEvent(sb, B->ev_cut, 0) != hipSuccess))
+        return ErrHip;
+    BatchParams tiers[kLdsTiers];
+    for (int t = 0; t < kLdsTiers; t++) {
+        tiers[t] = B->tier[t];
+        if (t != tb) tiers[t].n_list = 0;
+    }
+    BatchParams large = B->large;
+    large.n_list = 0;
+    large.fb_slots = 0;
+    ReplayLaunch r{};
+    r.lds = tiers;
+    r.n_lds = kLdsTiers;
+    r.large = &large;
+    r.stream = sb;
+    r.keep_fb = true;
+    return launch_replay(r);
+}
+// The main pipeline's prep and plan of a split pass (the documents outside the big tier).
+int launch_split_prep(dtgpu_batch *B, hipStream_t s) {
+    PrepParams pp = B->prep;
+    pp.doc_list = B->d_split.p + B->n_big;
+    pp.n_docs = B->n_rest;
+    return launch_prep(pp, s) ? ErrHip : OK;
+}
+int launch_split_plan(dtgpu_batch *B, hipStream_t s) {
+    if (!B->n_gpu_planned) return OK;
+    PlanParams qq = B->plan;
+    qq.doc_list = B->d_split.p + B->n_big;
+    qq.n_docs = B->n_rest;
+    return launch_plan(qq, s);
+}
+
+// Prep then plan for a device-staged batch.  With the three-launch prep and the walk kernel, the
+// walk (CSR mode: it needs only prep's first half) runs on B->wstream beside the chain
+// decomposition and prep's second half, and the plan kernel waits for it.  `mid` (nullable) is
+// recorded between the two on s.
+int prep_and_plan(dtgpu_batch *B, hipStream_t s, hipEvent_t mid) {
+    const bool prep = B->dec != nullptr;
+    const bool overlap = prep && B->n_gpu_planned && B->prep.chain_flag && !B->prep.check && B->plan.walk &&
+                         B->plan.coff && B->wstream && B->cfg.walk_overlap;
+    if (!overlap) {
+        if (prep && launch_prep(B->prep, s)) return ErrHip;
+        if (launch_cut(B->cut, s)) return ErrHip;   // (after prep: it reads the parents' entries)
+        if (mid && hipEventRecord(mid, s) != hipSuccess) return ErrHip;
+        return B->n_gpu_planned ? launch_plan(B->plan, s) : OK;
+    }
+    // the walk reads prep's CSR and, split, the planner only the entry records' heads
+    PrepParams pp = B->prep;
+    pp.short_rec = B->plan.split ? 1u : 0u;
+    if (launch_prep_stage(pp, s, 1)) return ErrHip;
+    if (hipEventRecord(B->ev_w0, s) != hipSuccess || hipStreamWaitEvent(B->wstream, B->ev_w0, 0) != hipSuccess) return ErrHip;
+    if (launch_walk(B->plan, B->wstream, true) != OK) return ErrHip;
+    if (hipEventRecord(B->ev_w1, B->wstream) != hipSuccess) return ErrHip;
+    // the cut planning after the walk (it reads prep's parent entries), beside prep's second half
+    // and the planner (only the replay needs it)
+    if (B->cut.n_groups && (launch_cut(B->cut, B->wstream) || hipEventRecord(B->ev_cut, B->wstream) != hipSuccess))
+        return ErrHip;
+    if (launch_prep_stage(pp, s, 2) || launch_prep_stage(pp, s, 3)) return ErrHip;
+    if (mid && hipEventRecord(mid, s) != hipSuccess) return ErrHip;
+    if (hipStreamWaitEvent(s, B->ev_w1, 0) != hipSuccess) return ErrHip;
+    if (launch_plan(B->plan, s, false) != OK) return ErrHip;
+    if (B->cut.n_groups && hipStreamWaitEvent(s, B->ev_cut, 0) != hipSuccess) return ErrHip;
+    return OK;
+}
+
+// The linear documents' checkout (dt_ff.hip) on s: first in a pass, or, in a split pass, right
+// after the side pipeline's fork (beside it, before the main pipeline's prep).
+int launch_ff_pass(dtgpu_batch *B, hipStream_t s) { return B->n_ff ? launch_ff(B->ff, s) : OK; }
+// The tracker part of a pass (prep -> plan -> replay), unless every document fast-forwards.
+bool tracker_pass(const dtgpu_batch *B) { return B->n_track != 0 || B->ff_doc.empty(); }
+
+// The events a timed pass records on s between its steps (all null: an untimed pass): at its
+// start, when the main pipeline's prep is enqueued, and when its plan is.
+struct PassMarks { hipEvent_t start = nullptr, prepped = nullptr, planned = nullptr; };
+int mark(hipEvent_t e, hipStream_t s) { return !e || hipEventRecord(e, s) == hipSuccess ? OK : ErrHip; }
+
+// One checkout pass on stream s: the pass mark, the split pass's side pipeline, the fast-forward
+// pass, prep (device-staged batches; split: the rest's prep), plan, replay.
+int launch_pass(dtgpu_batch *B, hipStream_t s, const PassMarks &m = {}) {
+    if (B->pass_mark && launch_pass_mark(s)) return ErrHip;
+    if (mark(m.start, s)) return ErrHip;
+    if (B->xf_mode) {   // host plans (n_gpu_planned is 0), every document on the HBM tier
+        if (mark(m.prepped, s)) return ErrHip;
+        if (B->n_gpu_planned && launch_plan(B->plan, s) != OK) return ErrHip;
+        return mark(m.planned, s) ? ErrHip : launch_replay_xf(B->large, s);
+    }
+    int e = B->split ? launch_split_side(B, s) : OK;   // (it plans the cuts too)
+    if (e) return e;
+    // a batch of only linear documents reports their pass as its replay time
+    const bool track = tracker_pass(B);
+    if (!track && (mark(m.prepped, s) || mark(m.planned, s))) return ErrHip;
+    e = launch_ff_pass(B, s);
+    if (e || !track) return e;
+    if (B->split) {   // prep / plan times are the main pipeline's
+        if ((e = launch_split_prep(B, s)) || (e = mark(m.prepped, s)) || (e = launch_split_plan(B, s))) return e;
+    } else if ((e = prep_and_plan(B, s, m.prepped))) {   // device-staged: walker inputs first
+        return e;
+    }
+    if (mark(m.planned, s)) return ErrHip;
+    return replay_all(B, s, B->split ? B->split_tier : -1);
+}
+
+}  // namespace
+
+extern "C" {
+
+dtgpu_status dtgpu_batch_xf_positions(dtgpu_batch *B, size_t i, uint32_t *out, size_t cap, size_t *n_out) {
+    if (!B || i >= B->n || !B->xf_mode) return DTGPU_ERR_ARG;
+    if (B->host_status[i] != OK) return dtgpu_status(B->host_status[i]);
+    const size_t n = size_t(B->n_lv[i]);
+    if (n_out) *n_out = n;
+    if (!out) return DTGPU_OK;
+    if (cap < n) return DTGPU_ERR_ARG;
+    DocResult r;
+    if (hipMemcpyAsync(&r, B->d_results.p + i, sizeof r, hipMemcpyDeviceToHost, B->stream) != hipSuccess ||
+        (n && hipMemcpyAsync(out, B->d_xf.p + B->docs[i].lv_off, n * 4, hipMemcpyDeviceToHost, B->stream) != hipSuccess) ||
+        hipStreamSynchronize(B->stream) != hipSuccess)
+        return DTGPU_ERR_HIP;
+    return r.status == OK ? DTGPU_OK : dtgpu_status(r.status);
+}
+dtgpu_status dtgpu_batch_run_e2e_timed(dtgpu_batch *B, float ms[4]) {
+    if (!B || !B->dec || B->dec->merged) return DTGPU_ERR_ARG;
+    if (hipSetDevice(B->device) != hipSuccess) return DTGPU_ERR_HIP;
+    hipStream_t s = B->stream;
+    // decode + prep + plan + replay from the `.dt` bytes in HBM
+    if (hipEventRecord(B->ev_dec, s) != hipSuccess) return DTGPU_ERR_HIP;
+    if (launch_decode(B->dec->P, s)) return DTGPU_ERR_HIP;
+    if (hipEventRecord(B->ev_prep, s) != hipSuccess) return DTGPU_ERR_HIP;
+    if (launch_ff_pass(B, s)) return DTGPU_ERR_HIP;   // linear documents (dt_ff.hip)
+    if (tracker_pass(B) ? prep_and_plan(B, s, B->ev0) != OK : hipEventRecord(B->ev0, s) != hipSuccess) return DTGPU_ERR_HIP;
+    if (hipEventRecord(B->ev_mid, s) != hipSuccess) return DTGPU_ERR_HIP;
+    int st = tracker_pass(B) ? replay_all(B, s) : OK;
+    if (st) return dtgpu_status(st);
+    if (hipEventRecord(B->ev1, s) != hipSuccess) return DTGPU_ERR_HIP;
+    if (hipEventSynchronize(B->ev1) != hipSuccess) return DTGPU_ERR_HIP;
+    float td = 0, tp = 0, tl = 0, tr = 0;
+    if (hipEventElapsedTime(&td, B->ev_dec, B->ev_prep) != hipSuccess || hipEventElapsedTime(&tp, B->ev_prep, B->ev0) != hipSuccess ||
+        hipEventElapsedTime(&tl, B->ev0, B->ev_mid) != hipSuccess || hipEventElapsedTime(&tr, B->ev_mid, B->ev1) != hipSuccess)
+        return DTGPU_ERR_HIP;
+    B->last_decode_ms = td; B->last_prep_ms = tp; B->last_plan_ms = tl; B->last_replay_ms = tr;
+    if (ms) { ms[0] = td; ms[1] = tp; ms[2] = tl; ms[3] = tr; }
+    return DTGPU_OK;
+}
+dtgpu_status dtgpu_batch_encode(dtgpu_batch *B, uint32_t flags, float *kernel_ms) {
+    if (!B || !B->dec || B->xf_mode) return DTGPU_ERR_ARG;
+    if (flags & ~uint32_t(DTGPU_ENCODE_FULL)) return DTGPU_ERR_ARG;
+    if (hipSetDevice(B->device) != hipSuccess) return DTGPU_ERR_HIP;
+    hipStream_t s = B->stream;
+#define CK(x) do { if (DTGPU_HIP_FAILED(x)) return DTGPU_ERR_HIP; } while (0)
+    if (B->e_desc.empty() && B->n) {   // layout once per batch
+        const dtgpu_decoded &Dd = *B->dec;
+        B->e_desc.assign(B->n, EncDesc{});
+        uint64_t w = 0, b = 0, o = 0;
+        uint32_t max_agents = 1, max_text = 0;
+        for (size_t i = 0; i < B->n; i++) {
+            EncDesc &e = B->e_desc[i];
+            e.skip = 1;
+            if (B->host_status[i] != OK) continue;
+            const DecodeResult &r = Dd.res[i];
+            const DecodeDesc &d = Dd.desc[i];
+            const DocDesc &dd = B->docs[i];
+            e.skip = 0;
+            e.in_off = d.in_off; e.arun_off = d.arun_off; e.ent_off = d.ent_off; e.poff_off = d.poff_off;
+            e.par_off = d.par_off; e.content_off = d.content_off; e.lv_off = d.lv_off; e.agent_off = d.agent_off;
+            e.cmd_off = dd.cmd_off;
+            e.ncmd = dd.ncmd; e.n_aruns = r.n_aruns; e.ne = r.n_entries; e.n_agents = r.n_agents;
+            e.n_lv = uint32_t(r.n_lv); e.n_content = r.n_content;
+            e.doc_id_off = r.doc_id_off; e.doc_id_len = r.doc_id_len;
+            e.w_off = w; w += enc_words(e.ne, e.ncmd, e.n_aruns, e.n_agents);
+            e.b_off = b; b += (r.n_content + lz4_bound(r.n_content) + 15) / 16 * 16;   // 16-B aligned text
+            // output bound: header + names + doc id + every stream at its widest varints
+            const uint64_t cap = 128 + 11ull * r.n_agents + 64 + (r.doc_id_len != 0xFFFFFFFFu ? r.doc_id_len : 0) +
+                                 30ull * (uint64_t(r.n_aruns) + r.n_entries) + 20ull * e.ncmd + 10ull * r.n_entries +
+                                 10ull * r.n_parents + lz4_bound(r.n_content) + d.in_len;   // names are in the input
+            e.out_off = o; e.out_cap = uint32_t(std::min<uint64_t>(cap, 0xFFFFFFF0ull)); o += (e.out_cap + 15) / 16 * 16;   // 16-B aligned (CRC reads)
+            max_agents = std::max(max_agents, r.n_agents);
+            max_text = std::max(max_text, r.n_content);
+        }
+        CK(B->e_docs.upload(B->e_desc, s));
+        CK(B->e_dres.alloc(B->n));
+        CK(B->e_w.alloc(std::max<uint64_t>(w, 1)));
+        CK(B->e_b.alloc(std::max<uint64_t>(b, 1)));
+        CK(B->e_out.alloc(std::max<uint64_t>(o, 1)));
+        EncParams &q = B->enc;
+        q.in = Dd.in.p; q.content = Dd.content.p;
+        q.aruns = Dd.aruns.p; q.ent = Dd.ent.p; q.poff = Dd.poff.p; q.par = Dd.par.p; q.cbyte = Dd.cbyte.p;
+        q.agents = Dd.agents.p;
+        q.cmds = B->d_cmds.p;
+        q.w = B->e_w.p; q.b = B->e_b.p; q.out = B->e_out.p;
+        q.docs = B->e_docs.p; q.results = B->e_dres.p;
+        q.n_docs = uint32_t(B->n);
+        q.max_agents = max_agents;
+        // kernel 2 stages a document's text in LDS for the LZ4 pass when it fits: 16 KiB of hash
+        // table + 512 B of output ring + <= 23.5 KiB of text keeps 4 waves per CU
+        // measured (10k friendsforever): 60 ms with the text in LDS (4 waves per CU), 44 ms with
+        // it read from HBM at 9 waves per CU -- occupancy wins in a batch, so staging is opt-in
+        q.lds_text = 0;
+        (void)max_text;
+        q.lds_text = B->cfg.enc_lds_text;
+        q.prof = B->cfg.enc_prof ? 1u : 0u;
+        for (int k = 0; k < 32; k++) q.x2n[k] = Dd.P.x2n[k];
+    }
+    // the walk order: the planner's commands (prep + plan, as a checkout pass runs them), for
+    // every document (a checkout pass skips the fast-forwarded ones: their lists cover the rest)
+    {
+        PrepParams pp = B->prep;
+        PlanParams qq = B->plan;
+        pp.doc_list = nullptr; pp.n_docs = uint32_t(B->n);
+        qq.doc_list = nullptr; qq.n_docs = uint32_t(B->n);
+        if (launch_prep(pp, s)) return DTGPU_ERR_HIP;
+        if (B->n_gpu_planned && launch_plan(qq, s) != OK) return DTGPU_ERR_HIP;
+    }
+    B->enc.flags = flags;
+    CK(hipMemsetAsync(B->e_dres.p, 0, std::max<size_t>(B->n, 1) * sizeof(EncResult), s));
+    CK(hipEventRecord(B->ev0, s));
+    if (launch_encode(B->enc, s)) return DTGPU_ERR_HIP;
+    CK(hipEventRecord(B->ev1, s));
+    B->e_res.resize(B->n);
+    CK(hipMemcpyAsync(B->e_res.data(), B->e_dres.p, B->n * sizeof(EncResult), hipMemcpyDeviceToHost, s));
+    CK(hipStreamSynchronize(s));
+    float ms = 0;
+    CK(hipEventElapsedTime(&ms, B->ev0, B->ev1));
+#undef CK
+    if (kernel_ms) *kernel_ms = ms;
+    return DTGPU_OK;
+}
+
+dtgpu_status dtgpu_batch_encoded(const dtgpu_batch *B, size_t i, uint8_t *out, size_t cap, size_t *out_len,
+                                 uint64_t prof[14]) {
+    if (!B || i >= B->n || B->e_res.size() != B->n) return DTGPU_ERR_ARG;
+    if (B->host_status[i] != OK) return dtgpu_status(B->host_status[i]);
+    const EncResult &r = B->e_res[i];
+    if (r.status != OK) return dtgpu_status(r.status);
+    if (prof) {
+        for (int k = 0; k < 6; k++) prof[k] = r.prof[k];
+        for (int k = 0; k < 3; k++) prof[6 + k] = r.lzcyc[k];
+        for (int k = 0; k < 3; k++) prof[9 + k] = r.lzst[k];
+        prof[12] = r.prof[6];
+        prof[13] = r.prof[7];
+    }
+    if (out_len) *out_len = r.len;
+    if (!out) return DTGPU_OK;
+    if (cap < r.len) return DTGPU_ERR_ARG;
+    if (hipSetDevice(B->device) != hipSuccess) return DTGPU_ERR_HIP;
+    if (hipMemcpy(out, B->e_out.p + B->e_desc[i].out_off, r.len, hipMemcpyDeviceToHost) != hipSuccess) return DTGPU_ERR_HIP;
+    return DTGPU_OK;
+}
+
+uint64_t dtgpu_batch_encoded_bytes(const dtgpu_batch *B, int which) {
+    if (!B || B->e_res.size() != B->n) return 0;
+    uint64_t t = 0;
+    for (size_t i = 0; i < B->n; i++) {
+        if (B->host_status[i] != OK || B->e_res[i].status != OK) continue;
+        const DecodeResult &r = B->dec->res[i];
+        if (which == 0) t += B->e_res[i].len;
+        else t += 16ull * r.n_ops + 8ull * r.n_entries + 4ull * r.n_parents + 16ull * r.n_aruns + r.n_content;
+    }
+    return t;
+}
+
+dtgpu_status dtgpu_batch_run(dtgpu_batch *B, void *stream) {
+    if (!B) return DTGPU_ERR_ARG;
+    if (hipSetDevice(B->device) != hipSuccess) return DTGPU_ERR_HIP;
+    void *s = stream ? stream : reinterpret_cast<void *>(B->stream);
+    if (B->debug)
+        fprintf(stderr, "[dtgpu] launch lds tiers %u/%u/%u/%u (blocks %u/%u/%u/%u) hbm %u\n", B->tier[0].n_list,
+                B->tier[1].n_list, B->tier[2].n_list, B->tier[3].n_list, B->tier[0].lds_blocks, B->tier[1].lds_blocks,
+                B->tier[2].lds_blocks, B->tier[3].lds_blocks, B->large.n_list);
+    if (B->debug) {
+        size_t nc = 0;
+        for (const DocDesc &d : B->docs) nc += (d.flags & DOC_CRITICAL) != 0;
+        fprintf(stderr, "[dtgpu] critical %zu of %zu replays; split tier %d (%u + %u documents)\n", nc, B->docs.size(),
+                B->split ? B->split_tier : -1, B->n_big, B->n_rest);
+    }
+    dtgpu_status st = dtgpu_status(launch_pass(B, reinterpret_cast<hipStream_t>(s)));
+    if (B->debug) {
+        fprintf(stderr, "[dtgpu] launched status %d\n", int(st));
+        hipError_t e = hipStreamSynchronize(reinterpret_cast<hipStream_t>(s));
+        fprintf(stderr, "[dtgpu] synced %d\n", int(e));
+    }
+    return st;
+}
+dtgpu_status dtgpu_batch_run_timed(dtgpu_batch *B, float *ms) {
+    if (!B) return DTGPU_ERR_ARG;
+    if (hipSetDevice(B->device) != hipSuccess) return DTGPU_ERR_HIP;
+    // one checkout pass of the whole batch on its stream: for device-staged batches the walker
+    // inputs (prep_kernel: parent entries, children CSR, chain decomposition -- what
+    // SpanningTreeWalker::new builds inside checkout_tip, txn_trace.rs:114-188), then the walk
+    // planner, then replay + materialisation
+    hipStream_t s = B->stream;
+    const bool prep = B->dec && !B->xf_mode;
+    if (const int st = launch_pass(B, s, PassMarks{B->ev_prep, B->ev0, B->ev_mid})) return dtgpu_status(st);
+    if (hipEventRecord(B->ev1, s) != hipSuccess) return DTGPU_ERR_HIP;
+    if (hipEventSynchronize(B->ev1) != hipSuccess) return DTGPU_ERR_HIP;
+    float t = 0, tp = 0, tq = 0;
+    if (hipEventElapsedTime(&t, B->ev_prep, B->ev1) != hipSuccess) return DTGPU_ERR_HIP;
+    if (hipEventElapsedTime(&tq, B->ev_prep, B->ev0) != hipSuccess) return DTGPU_ERR_HIP;
+    if (hipEventElapsedTime(&tp, B->ev0, B->ev_mid) != hipSuccess) return DTGPU_ERR_HIP;
+    B->last_prep_ms = prep ? tq : 0.0f;
+    B->last_plan_ms = tp;
+    B->last_replay_ms = t - tp - tq;
+    if (ms) *ms = t;
+    return DTGPU_OK;
+}
+dtgpu_status dtgpu_batch_sync(dtgpu_batch *B) {
+    if (!B) return DTGPU_ERR_ARG;
+    return hipStreamSynchronize(B->stream) == hipSuccess ? DTGPU_OK : DTGPU_ERR_HIP;
+}
+size_t dtgpu_batch_size(const dtgpu_batch *B) { return B ? B->n : 0; }
+dtgpu_status dtgpu_batch_last_times(const dtgpu_batch *B, float out[3]) {
+    if (!B || !out) return DTGPU_ERR_ARG;
+    out[0] = B->last_plan_ms;
+    out[1] = B->last_replay_ms;
+    out[2] = B->last_prep_ms;
+    return DTGPU_OK;
+}
+size_t dtgpu_batch_segments(dtgpu_batch *B, size_t doc, uint32_t *out, size_t cap) {
+    if (!B || doc >= B->n) return 0;
+    for (const SegGroup &g : B->seg_groups) {
+        if (B->seg_docs[g.first] != doc) continue;
+        if (hipSetDevice(B->device) != hipSuccess) return 0;
+        for (uint32_t k = 0; k < g.count && k < cap; k++) {
+            const uint32_t d = B->seg_docs[g.first + k];
+            DocDesc e{};   // the device descriptor: the pass's cut planning wrote the range
+            DocResult r{};
+            if (hipMemcpyAsync(&r, B->d_results.p + d, sizeof r, hipMemcpyDeviceToHost, B->stream) != hipSuccess ||
+                hipMemcpyAsync(&e, B->d_docs.p + d, sizeof e, hipMemcpyDeviceToHost, B->stream) != hipSuccess ||
+                hipStreamSynchronize(B->stream) != hipSuccess)
+                return 0;
+            uint32_t *w = out + 12 * size_t(k);
+            const size_t slot = size_t(g.first) + k;
+            const bool dev_cut = slot < B->seg_caps.size();   // device-staged: the pass plans the cuts
+            w[8] = dev_cut && (e.flags & DOC_CUT_HOST) ? 1u : 0u;
+            w[9] = dev_cut ? B->seg_caps[slot].lo : e.seg_lo;
+            w[10] = dev_cut ? B->seg_caps[slot].hi : e.seg_hi;
+            w[11] = dev_cut ? B->seg_caps[slot].u : e.seg_u;
+            w[0] = e.seg_lo; w[1] = e.seg_hi; w[2] = e.seg_u;
+            // the first segment's result slot is the document's: the combine step rewrote it
+            w[3] = k ? r.status : 0u; w[4] = k ? r.out_len : 0u; w[5] = r.dbg[15];
+            w[6] = r.lds; w[7] = r.n_blocks;
+        }
+        return g.count;
+    }
+    return 0;
+}
+size_t dtgpu_batch_host_planned(const dtgpu_batch *B, uint8_t *flags, size_t cap) {
+    if (!B) return 0;
+    if (flags) for (size_t i = 0; i < B->n && i < cap; i++) flags[i] = B->host_planned[i];
+    size_t k = 0;
+    for (uint8_t f : B->host_planned) k += f != 0;
+    return k;
+}
+size_t dtgpu_batch_fast_forwarded(const dtgpu_batch *B, uint8_t *flags, size_t cap) {
+    if (!B) return 0;
+    if (flags) for (size_t i = 0; i < B->n && i < cap; i++) flags[i] = i < B->ff_doc.size() ? B->ff_doc[i] : 0;
+    return B->n_ff;
+}
+dtgpu_status dtgpu_batch_plan(dtgpu_batch *B, size_t i, uint32_t *cmds, size_t cmd_cap, uint32_t *tlist,
+                              size_t tlist_cap, size_t *n_cmds, size_t *n_tlist) {
+    if (!B || i >= B->n) return DTGPU_ERR_ARG;
+    if (B->host_status[i] != OK) return dtgpu_status(B->host_status[i]);
+    if (i < B->ff_doc.size() && B->ff_doc[i]) {   // fast-forwarded: a checkout pass plans no walk for it
+        if (n_cmds) *n_cmds = 0;
+        if (n_tlist) *n_tlist = 0;
+        return DTGPU_OK;
+    }
+    const DocDesc &d = B->docs[i];
+    std::vector<Cmd> c(d.ncmd);
+    if (d.ncmd && hipMemcpyAsync(c.data(), B->d_cmds.p + d.cmd_off, d.ncmd * sizeof(Cmd), hipMemcpyDeviceToHost, B->stream) != hipSuccess)
+        return DTGPU_ERR_HIP;
+    if (hipStreamSynchronize(B->stream) != hipSuccess) return DTGPU_ERR_HIP;
+    size_t nt = 0;
+    for (const Cmd &x : c) if ((x.op & 15u) == CMD_TOG) nt = std::max<size_t>(nt, size_t(x.lv) + x.len);
+    if (n_cmds) *n_cmds = c.size();
+    if (n_tlist) *n_tlist = nt;
+    if (cmds) {
+        if (cmd_cap < c.size()) return DTGPU_ERR_ARG;
+        std::memcpy(cmds, c.data(), c.size() * sizeof(Cmd));
+    }
+    if (tlist && nt) {
+        if (tlist_cap < nt) return DTGPU_ERR_ARG;
+        if (hipMemcpyAsync(tlist, B->d_tlist.p + d.tlist_off, nt * 4, hipMemcpyDeviceToHost, B->stream) != hipSuccess ||
+            hipStreamSynchronize(B->stream) != hipSuccess)
+            return DTGPU_ERR_HIP;
+    }
+    return DTGPU_OK;
+}
+uint64_t dtgpu_batch_algorithmic_bytes(dtgpu_batch *B) {
+    if (!B) return 0;
+    std::vector<dtgpu_doc_result> r(B->n);
+    if (B->n && dtgpu_batch_results(B, r.data()) != DTGPU_OK) return 0;
+    uint64_t out = 0;
+    for (const auto &x : r) out += x.text_len;
+    return B->alg_in_bytes + out;
+}
+dtgpu_status dtgpu_batch_plan_profile(dtgpu_batch *B, size_t i, uint64_t out[8]) {
+    if (!B || i >= B->n || !out) return DTGPU_ERR_ARG;
+    PlanResult r;
+    if (hipMemcpyAsync(&r, B->p_results.p + i, sizeof r, hipMemcpyDeviceToHost, B->stream) != hipSuccess ||
+        hipStreamSynchronize(B->stream) != hipSuccess)
+        return DTGPU_ERR_HIP;
+    for (int k = 0; k < 6; k++) out[k] = r.prof[k];
+    out[6] = r.ncmd;
+    out[7] = r.ntlist;
+    return DTGPU_OK;
+}
+dtgpu_status dtgpu_batch_doc_stats(dtgpu_batch *B, size_t i, uint32_t out[29]) {
+    if (!B || i >= B->docs.size() || !out) return DTGPU_ERR_ARG;   // (past n: the segment documents)
+    DocResult r;
+    if (hipMemcpyAsync(&r, B->d_results.p + i, sizeof r, hipMemcpyDeviceToHost, B->stream) != hipSuccess ||
+        hipStreamSynchronize(B->stream) != hipSuccess)
+        return DTGPU_ERR_HIP;
+    out[0] = r.n_items; out[1] = r.n_blocks; out[2] = r.fail_cmd; out[3] = r.fail_site;
+    out[4] = B->docs[i].ncmd; out[5] = B->docs[i].max_blocks;
+    for (int k = 0; k < 16; k++) out[6 + k] = r.dbg[k];
+    out[22] = r.n_sb;
+    out[23] = r.lds;
+    for (int k = 0; k < 3; k++) out[24 + k] = r.dbg[16 + k];
+    out[27] = r.dbg[19];   // block loads that rebuilt stale masks
+    out[28] = r.dbg[20];   // block loads (not from the registers' cached block)
+    return DTGPU_OK;
+}
+uint64_t dtgpu_batch_total_lv(const dtgpu_batch *B) { return B ? B->total_lv : 0; }
+
+dtgpu_status dtgpu_batch_results(dtgpu_batch *B, dtgpu_doc_result *res) {
+    if (!B || (!res && B->n)) return DTGPU_ERR_ARG;
+    std::vector<DocResult> dr(B->n);
+    if (B->n && hipMemcpyAsync(dr.data(), B->d_results.p, B->n * sizeof(DocResult), hipMemcpyDeviceToHost, B->stream) != hipSuccess)
+        return DTGPU_ERR_HIP;
+    if (hipStreamSynchronize(B->stream) != hipSuccess) return DTGPU_ERR_HIP;
+    for (size_t i = 0; i < B->n; i++) {
+        res[i].status = B->host_status[i] != OK ? B->host_status[i] : dr[i].status;
+        res[i].reserved = 0;
+        res[i].text_len = res[i].status == OK ? dr[i].out_len : 0;
+        res[i].text_hash = res[i].status == OK ? dr[i].hash : 0;
+        res[i].n_lv = B->n_lv[i];
+    }
+    return DTGPU_OK;
+}
+dtgpu_status dtgpu_batch_text(dtgpu_batch *B, size_t i, uint8_t *out, size_t cap, size_t *out_len) {
+    if (!B || i >= B->n) return DTGPU_ERR_ARG;
+    if (B->host_status[i] != OK) return dtgpu_status(B->host_status[i]);
+    DocResult r;
+    if (hipMemcpyAsync(&r, B->d_results.p + i, sizeof r, hipMemcpyDeviceToHost, B->stream) != hipSuccess ||
+        hipStreamSynchronize(B->stream) != hipSuccess)
+        return DTGPU_ERR_HIP;
+    if (r.status != OK) {
+        if (B->debug)
+            fprintf(stderr, "[dtgpu] doc %zu status %u fail_cmd %u fail_site %u items %u blocks %u dbg %u %u %u %u %u %u %u %x %x %x\n", i, r.status,
+                    r.fail_cmd, r.fail_site, r.n_items, r.n_blocks, r.dbg[0], r.dbg[1], r.dbg[2], r.dbg[3], r.dbg[4],
+                    r.dbg[5], r.dbg[6], r.dbg[7], r.dbg[8], r.dbg[9]);
+        return dtgpu_status(r.status);
+    }
+    if (out_len) *out_len = r.out_len;
+    if (!out) return DTGPU_OK;
+    if (cap < r.out_len) return DTGPU_ERR_ARG;
+    if (r.out_len && (hipMemcpyAsync(out, B->d_out.p + B->docs[i].out_off, r.out_len, hipMemcpyDeviceToHost, B->stream) != hipSuccess ||
+                      hipStreamSynchronize(B->stream) != hipSuccess))
+        return DTGPU_ERR_HIP;
+    return DTGPU_OK;
+}
+void dtgpu_batch_free(dtgpu_batch *B) { delete B; }
+
+}  // extern "C"

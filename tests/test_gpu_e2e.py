@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import golden_data as G
+import linear_docs as L
 from oracle.oracle import OpLog as OracleOpLog
 
 pytestmark = pytest.mark.gpu
@@ -160,6 +161,30 @@ def test_mixed_errors_and_e2e_rerun():
     r3, t3 = [b.results(), [b.text(i) if r["status"] == 0 else None for i, r in enumerate(b.results())]]
     assert t3 == t1
 
+
+def test_host_and_device_staging_agree_on_the_layout():
+    """The two stagings (host decode with uploaded planner arrays, device decode with the prep
+    kernel) lay one batch out alike: a concurrent benchmark file, a synthetic merge document, a
+    linear document and two undecodable ones get the same statuses, the same fast-forward flags,
+    the same (oracle) texts, and, on the tracker, the same block capacity and command count."""
+    good = G.dt_bytes("friendsforever")
+    bad = bytearray(good)
+    bad[100] ^= 0xFF
+    docs = [good, dt_amd.synth_merge_oplog(0, 3000).encode(), L.sized_linear(200)[0], bytes(bad), b"nope"]
+    dev = dt_amd.Batch(docs=docs, staging="device")
+    host = dt_amd.Batch(docs=docs)
+    rd, td = _texts(dev)
+    rh, th = _texts(host)
+    assert [r["status"] for r in rd] == [r["status"] for r in rh]
+    assert [r["status"] == 0 for r in rd] == [True, True, True, False, False]
+    assert dev.fast_forwarded() == host.fast_forwarded() == [0, 0, 1, 0, 0]
+    assert td == th
+    for d, t in zip(docs, td):
+        if t is not None:
+            assert t == OracleOpLog.load_from(d).checkout_tip_bytes()
+    for i in (0, 1):   # the tracker documents
+        sd, sh = dev.doc_stats(i), host.doc_stats(i)
+        assert (sd["max_blocks"], sd["n_cmds"]) == (sh["max_blocks"], sh["n_cmds"]), i
 
 
 def test_document_past_the_block_limit():

@@ -102,7 +102,7 @@ def test_mixed_skewed_batch_forced_segments(mixed, monkeypatch):
 @pytest.mark.parametrize("critical", ["1", "0"])
 def test_configs4_batch_critical_documents(mixed, monkeypatch, critical):
     """configs[4] as bench.py runs it (all 8 traces x 50, round-robin): git-makefile's uncut
-    documents are the batch's critical replays (dtgpu_api.cpp mark_critical: first in their
+    documents are the batch's critical replays (dtgpu_stage.cpp mark_critical: first in their
     tier, top wave priority, their tier in the split pipeline with its overlapped walk); with
     DTGPU_CRITICAL=0 none are.  Every text either way equals the golden / oracle text."""
     docs, want = mixed

@@ -135,7 +135,7 @@ def _scattered_inserts_doc(seed, n_ins=400):
     """A concurrent prefix (two agents, then a merge: the history has cut points only after it),
     then long inserts (16-48 chars) scattered over the whole text and a few deletes: with small
     segments each later segment's inserts land across many placeholder blocks, the case the
-    block reservation of add_segments (dtgpu_api.cpp) bounds."""
+    block reservation of add_segments (dtgpu_stage.cpp) bounds."""
     import random
     rng = random.Random(seed)
     o = dt_amd.ListOpLog()
