@@ -38,6 +38,8 @@ struct Settings {
     uint32_t seg_w = SEG_W_OP; // the cut planner's cost weight of an op run
     bool seg_fair = true;      // the fair-share floor on seg_ops
     bool seg_late = true;      // late documents of the smallest tier cut once
+    bool late_pipe = true;     // ... and prepared, planned and replayed in a pipeline of their own
+    uint64_t late_from = 0;    // the flat tier's resident round in documents (0: from the device; tests)
     // expected inserted chars per block when sizing a document's LDS index: blocks end up ~43
     // items full on the benchmark traces (cut_point, dt_replay.hip), sized at 40 (tests force the
     // LDS overflow -> HBM tier hand-back with a large value)
@@ -118,6 +120,18 @@ struct dtgpu_batch {
     int split_tier = -1;
     uint32_t n_big = 0, n_rest = 0;
     DevBuf<uint32_t> d_split;
+    // device-staged late pipeline (Settings::late_pipe): the flat tier's documents past its first
+    // resident round run prep -> plan -> replay on side[0] (their walk on side[1]), so that the
+    // first round's replay starts without them (dtgpu_pass.cpp launch_late_pass).  d_late: the
+    // first round's documents and every document outside
+    // the flat tier (n_first), then the late ones (n_late), laid out as d_split; the flat tier's
+    // replay list holds the first round's workgroups (flat_first), then the late documents'.
+    // Never with a split pass.
+    bool late_pipe = false;
+    std::vector<uint8_t> late_doc;   // per document: 1 = in the late pipeline (empty: no late set)
+    uint32_t n_first = 0, n_late = 0, flat_first = 0;
+    DevBuf<uint32_t> d_late;
+    hipEvent_t ev_lprep = nullptr, ev_lgo = nullptr;   // the late prep is done; the late plan may start
     uint64_t alg_in_bytes = 0, total_lv = 0;
     float last_plan_ms = 0, last_replay_ms = 0;
 
@@ -209,7 +223,7 @@ struct dtgpu_batch {
     dtgpu::EncParams enc{};
 
     ~dtgpu_batch() {
-        for (hipEvent_t e : {ev_splan, ev_cut, ev_sw0, ev_sw1, ev_w0, ev_w1, ev_dec, ev_prep, ev0, ev_mid, ev1, ev_fork})
+        for (hipEvent_t e : {ev_lprep, ev_lgo, ev_splan, ev_cut, ev_sw0, ev_sw1, ev_w0, ev_w1, ev_dec, ev_prep, ev0, ev_mid, ev1, ev_fork})
             if (e) (void)hipEventDestroy(e);
         if (ws_side) (void)hipStreamDestroy(ws_side);
         for (int k = 0; k < dtgpu::kSideStreams; k++) {

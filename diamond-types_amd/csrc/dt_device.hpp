@@ -93,10 +93,11 @@ struct BatchParams {
     uint32_t *xf;
     uint32_t *src;   // cut replay: the segments' source lists (DocDesc::src_off)
     uint32_t lds_flat;   // LDS tiers: 1 = the flat 2-level index (IX_FLAT), 0 = the 3-level one
-    uint32_t prio_from;  // LDS tiers: workgroups from this index on (dispatched after the first
-                         // resident set) raise their wave priority (0: off)
+    uint32_t prio_from;  // LDS tiers: workgroups from index prio_from - 1 on (dispatched after the
+                         // first resident set) raise their wave priority (0: off, 1: all of them)
     uint32_t n_cu;       // compute units of the batch's device (resident-set sizes)
     uint32_t prio_on;    // LDS tiers: late workgroups raise their priority (prio_from computed at launch)
+    uint32_t all_late;   // flat tier: the launch holds only late workgroups (the late pipeline's replay)
     uint32_t tog_waves;  // 1: retreat / advance passes on one wave; else helper waves on the big tiers
     uint32_t tog_mw_lds; // LDS index bytes from which a tier gets helper waves
 };

@@ -1723,7 +1723,7 @@ __global__ __launch_bounds__(MW ? 64 * TOG_WAVES : 64) __attribute__((amdgpu_wav
     // on its SIMD, and the arbiter serves older waves first: such a late document would run to
     // the end of the batch at the back of the queue.  It takes the higher priority instead, so
     // the batch's last documents finish beside the first round's slowest ones.
-    if (P.prio_from && di >= P.prio_from) __builtin_amdgcn_s_setprio(3);
+    if (P.prio_from && di + 1 >= P.prio_from) __builtin_amdgcn_s_setprio(3);
     uint32_t d;
     if (di < P.n_list) {
         d = U(P.doc_list[di]);
@@ -1895,7 +1895,7 @@ static int launch_lds_tier(const BatchParams &q, hipStream_t s, bool prof) {
             // (the batch's own device: late_documents sizes the same resident set from it)
             const size_t gran = (lds + 1279) / 1280 * 1280;
             const size_t per_cu = std::min<size_t>(32, 163840 / std::max<size_t>(gran, 1280));
-            qp.prio_from = uint32_t(per_cu * size_t(std::max<uint32_t>(q.n_cu, 1)));
+            qp.prio_from = q.all_late ? 1u : uint32_t(per_cu * size_t(std::max<uint32_t>(q.n_cu, 1))) + 1;
         }
         if (prof) hipLaunchKernelGGL((dev::replay_kernel<dev::IX_FLAT, true, false>), dim3(q.n_list), dim3(64), lds, s, qp);
         else hipLaunchKernelGGL((dev::replay_kernel<dev::IX_FLAT, false, false, false, 8>), dim3(q.n_list), dim3(64), lds, s, qp);

@@ -104,37 +104,62 @@ int launch_split_plan(dtgpu_batch *B, hipStream_t s) {
     return launch_plan(qq, s);
 }
 
-// Prep then plan for a device-staged batch.  With the three-launch prep and the walk kernel, the
-// walk (CSR mode: it needs only prep's first half) runs on B->wstream beside the chain
-// decomposition and prep's second half, and the plan kernel waits for it.  `mid` (nullable) is
-// recorded between the two on s.
-int prep_and_plan(dtgpu_batch *B, hipStream_t s, hipEvent_t mid) {
-    const bool prep = B->dec != nullptr;
-    const bool overlap = prep && B->n_gpu_planned && B->prep.chain_flag && !B->prep.check && B->plan.walk &&
-                         B->plan.coff && B->wstream && B->cfg.walk_overlap;
-    if (!overlap) {
-        if (prep && launch_prep(B->prep, s)) return ErrHip;
-        if (launch_cut(B->cut, s)) return ErrHip;   // (after prep: it reads the parents' entries)
-        if (mid && hipEventRecord(mid, s) != hipSuccess) return ErrHip;
-        return B->n_gpu_planned ? launch_plan(B->plan, s) : OK;
+// Prep then plan for a device-staged batch, as one pipeline: its documents (doc_list / n_docs of
+// prep and plan), its cut groups, its stream, its walk stream and the events between the two (w0:
+// prep's first half is done).  A whole pass has one pipeline over B's own parameters, a
+// late-pipeline pass two.  With the three-launch prep and the walk kernel, the walk (CSR mode: it
+// needs only prep's first half) runs on the walk stream beside the chain decomposition and prep's
+// second half, and the plan kernel waits for it; the pipeline's cut planning (if it has cut groups)
+// follows the walk there.
+struct Pipe {
+    PrepParams prep;
+    PlanParams plan;
+    CutParams cut;
+    hipStream_t s, w;
+    hipEvent_t w0, w1, cut_done;
+};
+Pipe whole_pipe(const dtgpu_batch *B, hipStream_t s) {
+    return Pipe{B->prep, B->plan, B->cut, s, B->wstream, B->ev_w0, B->ev_w1, B->ev_cut};
+}
+bool walk_beside(const dtgpu_batch *B, const Pipe &p) {
+    return B->dec && B->n_gpu_planned && p.prep.chain_flag && !p.prep.check && p.plan.walk && p.plan.coff && p.w &&
+           B->cfg.walk_overlap;
+}
+// The prep half; `mid` (nullable) is recorded at its end on s.
+int pipe_prep(dtgpu_batch *B, const Pipe &p, hipEvent_t mid) {
+    hipStream_t s = p.s;
+    if (!walk_beside(B, p)) {
+        if (B->dec && launch_prep(p.prep, s)) return ErrHip;
+        if (p.w0 && hipEventRecord(p.w0, s) != hipSuccess) return ErrHip;
+        if (launch_cut(p.cut, s)) return ErrHip;   // (after prep: it reads the parents' entries)
+        return mid && hipEventRecord(mid, s) != hipSuccess ? ErrHip : OK;
     }
     // the walk reads prep's CSR and, split, the planner only the entry records' heads
-    PrepParams pp = B->prep;
-    pp.short_rec = B->plan.split ? 1u : 0u;
+    PrepParams pp = p.prep;
+    pp.short_rec = p.plan.split ? 1u : 0u;
     if (launch_prep_stage(pp, s, 1)) return ErrHip;
-    if (hipEventRecord(B->ev_w0, s) != hipSuccess || hipStreamWaitEvent(B->wstream, B->ev_w0, 0) != hipSuccess) return ErrHip;
-    if (launch_walk(B->plan, B->wstream, true) != OK) return ErrHip;
-    if (hipEventRecord(B->ev_w1, B->wstream) != hipSuccess) return ErrHip;
+    if (hipEventRecord(p.w0, s) != hipSuccess || hipStreamWaitEvent(p.w, p.w0, 0) != hipSuccess) return ErrHip;
+    if (launch_walk(p.plan, p.w, true) != OK) return ErrHip;
+    if (hipEventRecord(p.w1, p.w) != hipSuccess) return ErrHip;
     // the cut planning after the walk (it reads prep's parent entries), beside prep's second half
     // and the planner (only the replay needs it)
-    if (B->cut.n_groups && (launch_cut(B->cut, B->wstream) || hipEventRecord(B->ev_cut, B->wstream) != hipSuccess))
+    if (p.cut.n_groups && (launch_cut(p.cut, p.w) || hipEventRecord(p.cut_done, p.w) != hipSuccess))
         return ErrHip;
     if (launch_prep_stage(pp, s, 2) || launch_prep_stage(pp, s, 3)) return ErrHip;
-    if (mid && hipEventRecord(mid, s) != hipSuccess) return ErrHip;
-    if (hipStreamWaitEvent(s, B->ev_w1, 0) != hipSuccess) return ErrHip;
-    if (launch_plan(B->plan, s, false) != OK) return ErrHip;
-    if (B->cut.n_groups && hipStreamWaitEvent(s, B->ev_cut, 0) != hipSuccess) return ErrHip;
+    return mid && hipEventRecord(mid, s) != hipSuccess ? ErrHip : OK;
+}
+// The plan half: after it, s may replay the pipeline's documents.
+int pipe_plan(dtgpu_batch *B, const Pipe &p) {
+    hipStream_t s = p.s;
+    const bool beside = walk_beside(B, p);
+    if (beside && hipStreamWaitEvent(s, p.w1, 0) != hipSuccess) return ErrHip;
+    if (B->n_gpu_planned && launch_plan(p.plan, s, !beside) != OK) return ErrHip;
+    if (beside && p.cut.n_groups && hipStreamWaitEvent(s, p.cut_done, 0) != hipSuccess) return ErrHip;
     return OK;
+}
+int prep_and_plan(dtgpu_batch *B, const Pipe &p, hipEvent_t mid) {
+    const int e = pipe_prep(B, p, mid);
+    return e ? e : pipe_plan(B, p);
 }
 
 // The linear documents' checkout (dt_ff.hip) on s: first in a pass, or, in a split pass, right
@@ -147,6 +172,94 @@ bool tracker_pass(const dtgpu_batch *B) { return B->n_track != 0 || B->ff_doc.em
 // start, when the main pipeline's prep is enqueued, and when its plan is.
 struct PassMarks { hipEvent_t start = nullptr, prepped = nullptr, planned = nullptr; };
 int mark(hipEvent_t e, hipStream_t s) { return !e || hipEventRecord(e, s) == hipSuccess ? OK : ErrHip; }
+
+// A replay launch of `count` workgroups of the flat tier's list from `first` on, nothing else.
+int replay_flat_range(dtgpu_batch *B, hipStream_t s, uint32_t first, uint32_t count, bool all_late) {
+    BatchParams tiers[kLdsTiers];
+    for (int t = 0; t < kLdsTiers; t++) { tiers[t] = B->tier[t]; tiers[t].n_list = 0; }
+    tiers[0].doc_list = B->tier[0].doc_list + first;
+    tiers[0].n_list = count;
+    tiers[0].all_late = all_late ? 1u : 0u;
+    BatchParams large = B->large;
+    large.n_list = 0;
+    large.fb_slots = 0;
+    ReplayLaunch r{};   // (no side streams: one tier)
+    r.lds = tiers;
+    r.n_lds = kLdsTiers;
+    r.large = &large;
+    r.stream = s;
+    r.keep_fb = true;
+    return launch_replay(r);
+}
+// A pass with the late pipeline (dt_batch.hpp late_pipe).  On s: prep and plan of the first
+// round's documents, then their replay.  On side[0] (the walk on side[1]), from the end of the
+// main pipeline's prep first half on -- the two first halves share no round: the late
+// documents' prep, beside the main pipeline's prep and plan.  The cut planning of both sets in
+// one launch, where a whole pass has it: on the main pipeline's walk stream after its walk,
+// beside the main plan (measured: on the late streams it waits for slots for 3 ms and holds up
+// the late chain decomposition, or, after the first round's replay, the late replay).  The first
+// round's replay fills every wave slot of the device and its whole documents are the pass's
+// critical path, so it must not find a slot taken: s waits for the late prep and the cuts
+// (nothing else is in flight then), and the late plan opens one event hop (over the walk stream)
+// after the first round's replay is launched -- it and the late replay, every workgroup at the
+// raised priority, then queue for the slots the first round frees.  s joins side[0] before the
+// HBM tier (its own documents and whatever either launch handed back) and the combine step.
+// The marks are the main pipeline's, as in a split pass.
+int launch_late_pass(dtgpu_batch *B, hipStream_t s, const PassMarks &m) {
+    hipStream_t sl = B->side[0];
+    const BatchParams &q = B->tier[0];
+    if (q.fb_count && hipMemsetAsync(const_cast<uint32_t *>(q.fb_count), 0, sizeof(uint32_t), s) != hipSuccess) return ErrHip;
+    Pipe a = whole_pipe(B, s);
+    a.prep.doc_list = a.plan.doc_list = B->d_late.p;
+    a.prep.n_docs = a.plan.n_docs = B->n_first;
+    a.cut.n_groups = 0;   // (below, for both pipelines)
+    Pipe b = whole_pipe(B, sl);
+    b.prep.doc_list = b.plan.doc_list = B->d_late.p + B->n_first;
+    b.prep.n_docs = b.plan.n_docs = B->n_late;
+    b.cut.n_groups = 0;
+    b.w = B->side[1]; b.w0 = B->ev_sw0; b.w1 = B->ev_sw1; b.cut_done = nullptr;
+    int e = pipe_prep(B, a, m.prepped);
+    if (e) return e;
+    if (hipStreamWaitEvent(sl, B->ev_w0, 0) != hipSuccess || (e = pipe_prep(B, b, nullptr))) return e ? e : ErrHip;
+    if (walk_beside(B, b) && hipStreamWaitEvent(sl, b.w1, 0) != hipSuccess) return ErrHip;
+    if (hipEventRecord(B->ev_lprep, sl) != hipSuccess) return ErrHip;
+    if (B->cut.n_groups) {   // (it reads both first halves' parent entries)
+        hipStream_t w = B->wstream;
+        if (hipStreamWaitEvent(w, B->ev_w0, 0) != hipSuccess || hipStreamWaitEvent(w, B->ev_sw0, 0) != hipSuccess ||
+            launch_cut(B->cut, w) || hipEventRecord(B->ev_cut, w) != hipSuccess)
+            return ErrHip;
+    }
+    if ((e = pipe_plan(B, a)) || (e = mark(m.planned, s))) return e;
+    if (hipStreamWaitEvent(s, B->ev_lprep, 0) != hipSuccess || (B->cut.n_groups && hipStreamWaitEvent(s, B->ev_cut, 0) != hipSuccess) ||
+        hipEventRecord(B->ev_fork, s) != hipSuccess)
+        return ErrHip;
+    if ((e = replay_flat_range(B, s, 0, B->flat_first, false))) return e;
+    if (hipStreamWaitEvent(B->wstream, B->ev_fork, 0) != hipSuccess || hipEventRecord(B->ev_lgo, B->wstream) != hipSuccess ||
+        hipStreamWaitEvent(sl, B->ev_lgo, 0) != hipSuccess)
+        return ErrHip;
+    if ((e = pipe_plan(B, b))) return e;
+    if ((e = replay_flat_range(B, sl, B->flat_first, q.n_list - B->flat_first, true))) return e;
+    if (hipEventRecord(B->ev_join[0], sl) != hipSuccess || hipStreamWaitEvent(s, B->ev_join[0], 0) != hipSuccess) return ErrHip;
+    // the HBM tier and the combine step, as replay_all's
+    BatchParams none[kLdsTiers];
+    for (int t = 0; t < kLdsTiers; t++) { none[t] = B->tier[t]; none[t].n_list = 0; }
+    ReplayLaunch r{};
+    r.lds = none;
+    r.n_lds = kLdsTiers;
+    r.large = &B->large;
+    r.stream = s;
+    r.keep_fb = true;
+    e = launch_replay(r);
+    return e ? e : launch_combine(B->comb, s);
+}
+// The tracker part of a pass on s, after the fast-forward pass: prep (device-staged: the walker
+// inputs first), plan, replay -- every entry point's, timed or not.
+int launch_tracker(dtgpu_batch *B, hipStream_t s, const PassMarks &m) {
+    if (B->late_pipe) return launch_late_pass(B, s, m);
+    int e = prep_and_plan(B, whole_pipe(B, s), m.prepped);
+    if (e || (e = mark(m.planned, s))) return e;
+    return replay_all(B, s);
+}
 
 // One checkout pass on stream s: the pass mark, the split pass's side pipeline, the fast-forward
 // pass, prep (device-staged batches; split: the rest's prep), plan, replay.
@@ -165,13 +278,11 @@ int launch_pass(dtgpu_batch *B, hipStream_t s, const PassMarks &m = {}) {
     if (!track && (mark(m.prepped, s) || mark(m.planned, s))) return ErrHip;
     e = launch_ff_pass(B, s);
     if (e || !track) return e;
-    if (B->split) {   // prep / plan times are the main pipeline's
-        if ((e = launch_split_prep(B, s)) || (e = mark(m.prepped, s)) || (e = launch_split_plan(B, s))) return e;
-    } else if ((e = prep_and_plan(B, s, m.prepped))) {   // device-staged: walker inputs first
-        return e;
-    }
+    if (!B->split) return launch_tracker(B, s, m);
+    // prep / plan times are the main pipeline's
+    if ((e = launch_split_prep(B, s)) || (e = mark(m.prepped, s)) || (e = launch_split_plan(B, s))) return e;
     if (mark(m.planned, s)) return ErrHip;
-    return replay_all(B, s, B->split ? B->split_tier : -1);
+    return replay_all(B, s, B->split_tier);
 }
 
 }  // namespace
@@ -201,9 +312,9 @@ dtgpu_status dtgpu_batch_run_e2e_timed(dtgpu_batch *B, float ms[4]) {
     if (launch_decode(B->dec->P, s)) return DTGPU_ERR_HIP;
     if (hipEventRecord(B->ev_prep, s) != hipSuccess) return DTGPU_ERR_HIP;
     if (launch_ff_pass(B, s)) return DTGPU_ERR_HIP;   // linear documents (dt_ff.hip)
-    if (tracker_pass(B) ? prep_and_plan(B, s, B->ev0) != OK : hipEventRecord(B->ev0, s) != hipSuccess) return DTGPU_ERR_HIP;
-    if (hipEventRecord(B->ev_mid, s) != hipSuccess) return DTGPU_ERR_HIP;
-    int st = tracker_pass(B) ? replay_all(B, s) : OK;
+    // (the same tracker pass as dtgpu_batch_run's, its marks between prep, plan and replay)
+    const int st = tracker_pass(B) ? launch_tracker(B, s, PassMarks{nullptr, B->ev0, B->ev_mid})
+                                   : (mark(B->ev0, s) || mark(B->ev_mid, s) ? ErrHip : OK);
     if (st) return dtgpu_status(st);
     if (hipEventRecord(B->ev1, s) != hipSuccess) return DTGPU_ERR_HIP;
     if (hipEventSynchronize(B->ev1) != hipSuccess) return DTGPU_ERR_HIP;
@@ -428,6 +539,11 @@ size_t dtgpu_batch_fast_forwarded(const dtgpu_batch *B, uint8_t *flags, size_t c
     if (!B) return 0;
     if (flags) for (size_t i = 0; i < B->n && i < cap; i++) flags[i] = i < B->ff_doc.size() ? B->ff_doc[i] : 0;
     return B->n_ff;
+}
+size_t dtgpu_batch_late_pipelined(const dtgpu_batch *B, uint8_t *flags, size_t cap) {
+    if (!B || !B->late_pipe) return 0;
+    if (flags) for (size_t i = 0; i < B->n && i < cap; i++) flags[i] = B->late_doc[i];
+    return B->n_late;
 }
 dtgpu_status dtgpu_batch_plan(dtgpu_batch *B, size_t i, uint32_t *cmds, size_t cmd_cap, uint32_t *tlist,
                               size_t tlist_cap, size_t *n_cmds, size_t *n_tlist) {

@@ -38,6 +38,8 @@ Settings settings_for(const dtgpu_batch_opts *o) {
     x = c.seg_w; num("DTGPU_SEG_W", 0, 1u << 20, x); c.seg_w = uint32_t(x);
     on("DTGPU_SEG_FAIR", c.seg_fair);
     on("DTGPU_SEG_LATE", c.seg_late);
+    on("DTGPU_LATE_PIPE", c.late_pipe);
+    num("DTGPU_LATE_FROM", 1, UINT64_MAX, c.late_from);
     num("DTGPU_LDS_FILL", 1, UINT64_MAX, c.lds_fill);
     on("DTGPU_FLAT", c.flat);
     on("DTGPU_PLAN_SPLIT", c.plan_split);
@@ -231,6 +233,7 @@ size_t n_lds_docs(const dtgpu_batch &B) {
     for (int t = 0; t < kLdsTiers; t++) k += B.tier_list[t].size();
     return k;
 }
+std::vector<uint32_t> segment_owners(const dtgpu_batch &B);
 // Launch order of the documents: the LDS tiers, then the HBM tier; inside a list the documents
 // go by descending LVs (a cut document's first segment by its own), so the hardware dispatcher
 // starts the longest replays first (LPT inside the GPU: the short ones fill in behind them), the
@@ -244,10 +247,19 @@ std::vector<uint32_t> tier_lists(dtgpu_batch &B) {
             return d < B.first_cost.size() && B.first_cost[d] ? B.first_cost[d] : B.n_lv[d];
         };
         std::stable_sort(v.begin(), v.end(), [&](uint32_t a, uint32_t b) { return cost(a) > cost(b); });
-        append(all, v);
     };
-    for (int t = 0; t < kLdsTiers; t++) by_cost(B.tier_list[t]);
+    for (int t = 0; t < kLdsTiers; t++) {
+        std::vector<uint32_t> &v = B.tier_list[t];
+        by_cost(v);
+        if (t == 0 && B.late_pipe) {   // the first round's workgroups, then the late documents' (both halves of a cut one)
+            const std::vector<uint32_t> owner = segment_owners(B);
+            const auto mid = std::stable_partition(v.begin(), v.end(), [&](uint32_t d) { return !B.late_doc[owner[d]]; });
+            B.flat_first = uint32_t(mid - v.begin());
+        }
+        append(all, v);
+    }
     by_cost(B.large_list);
+    append(all, B.large_list);
     return all;
 }
 // The replay tiers' parameters: the arenas (cbyte / content: the batch's uploads, or the
@@ -292,7 +304,12 @@ dtgpu_status set_tier_params(dtgpu_batch &B, const uint32_t *cbyte, const uint8_
     B.debug = base.debug;
     if (!B.ev_fork) CK(hipEventCreateWithFlags(&B.ev_fork, hipEventDisableTiming));
     if (!B.ev_splan) CK(hipEventCreateWithFlags(&B.ev_splan, hipEventDisableTiming));
+    // the late pipeline's two streams at the lowest priority: whenever workgroups of both pipelines
+    // wait for a slot, the first round's go first (its whole documents are the pass's critical path)
+    int prio_least = 0, prio_greatest = 0;
+    if (B.late_pipe) CK(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
     for (int k = 0; k < kSideStreams; k++) {
+        if (!B.side[k] && B.late_pipe && k < 2) CK(hipStreamCreateWithPriority(&B.side[k], hipStreamNonBlocking, prio_least));
         if (!B.side[k]) CK(hipStreamCreateWithFlags(&B.side[k], hipStreamNonBlocking));
         if (!B.ev_join[k]) CK(hipEventCreateWithFlags(&B.ev_join[k], hipEventDisableTiming));
     }
@@ -380,19 +397,46 @@ std::vector<uint32_t> seg_candidates(size_t n, SegSettings &sc, int n_cu, bool f
 // to finish and would run to the end of the batch at low occupancy; each is cut once where its
 // history allows, so its two halves finish earlier beside each other.  (Device-staged batches:
 // the pass itself plans the cut, cut_kernel.)
+// The flat tier's documents longest first, and how many of them one resident round holds
+// (DTGPU_LATE_FROM overrides the device's figure: a small test batch then has a late set).
+struct FlatRounds { std::vector<uint32_t> order; size_t resident = 0; };
+FlatRounds flat_rounds(const dtgpu_batch &B) {
+    FlatRounds r;
+    if (B.tier_list[0].empty() || !B.cfg.flat || B.tier_blocks[0] > FLAT_MAX_BLOCKS) return r;
+    const size_t lds = size_t(flat_index_bytes(B.tier_blocks[0]));
+    const size_t gran = (lds + 1279) / 1280 * 1280;
+    r.resident = std::min<size_t>(32, 163840 / std::max<size_t>(gran, 1280)) * size_t(std::max(B.n_cu, 1));
+    if (B.cfg.late_from) r.resident = size_t(std::min<uint64_t>(B.cfg.late_from, SIZE_MAX));
+    r.order.assign(B.tier_list[0].begin(), B.tier_list[0].end());
+    std::stable_sort(r.order.begin(), r.order.end(), [&](uint32_t a, uint32_t b) { return B.n_lv[a] > B.n_lv[b]; });
+    return r;
+}
 template <typename NOps>
 std::vector<uint8_t> late_documents(const dtgpu_batch &B, const SegSettings &sc, NOps n_ops) {
     std::vector<uint8_t> late(B.n, 0);
-    if (!sc.on || !B.cfg.seg_late || B.tier_list[0].empty() || !B.cfg.flat || B.tier_blocks[0] > FLAT_MAX_BLOCKS) return late;
-    const size_t lds = size_t(flat_index_bytes(B.tier_blocks[0]));
-    const size_t gran = (lds + 1279) / 1280 * 1280;
-    const size_t resident = std::min<size_t>(32, 163840 / std::max<size_t>(gran, 1280)) * size_t(std::max(B.n_cu, 1));
-    std::vector<uint32_t> order(B.tier_list[0].begin(), B.tier_list[0].end());
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return B.n_lv[a] > B.n_lv[b]; });
+    if (!sc.on || !B.cfg.seg_late) return late;
+    const FlatRounds r = flat_rounds(B);
+    const size_t resident = r.resident;
+    const std::vector<uint32_t> &order = r.order;
     // (a batch of many rounds: its last round's worth, the documents that end the batch)
     const size_t from = std::max(resident, order.size() > resident ? order.size() - resident : size_t(0));
     for (size_t k = from; k < order.size(); k++)
         if (order[k] < B.n && n_ops(order[k]) >= 128) late[order[k]] = 1;
+    return late;
+}
+// The late pipeline's documents (dt_batch.hpp late_pipe): every flat-tier document past the first
+// resident round, cut or not, when the tier has fewer than two rounds' worth (a batch of many rounds
+// keeps the GPU full with one pipeline: DESIGN §5a found late cutting neutral there) and no other
+// LDS tier has documents -- those tiers replay on the side streams the late pipeline runs on, and
+// with the split pass on (the default) such a batch is a split pass, which wins: the two are never
+// combined.  Empty: no late pipeline.
+std::vector<uint8_t> late_pipe_documents(const dtgpu_batch &B) {
+    if (!B.cfg.late_pipe) return {};
+    for (int t = 1; t < kLdsTiers; t++) if (!B.tier_list[t].empty()) return {};
+    const FlatRounds r = flat_rounds(B);
+    if (!r.resident || r.order.size() <= r.resident || r.order.size() >= 2 * r.resident) return {};
+    std::vector<uint8_t> late(B.n, 0);
+    for (size_t k = r.resident; k < r.order.size(); k++) late[r.order[k]] = 1;
     return late;
 }
 // Per replay document, the document it belongs to: a segment document's document, else itself.
@@ -923,6 +967,8 @@ dtgpu_status stage_device(dtgpu_decoded *dec, const dtgpu_batch_opts *opts, dtgp
         std::vector<uint32_t> all = cand;
         for (size_t i = 0; i < n; i++) if (late[i]) all.push_back(uint32_t(i));
         std::sort(all.begin(), all.end());
+        B->late_doc = late_pipe_documents(*B);
+        B->late_pipe = !B->late_doc.empty();
         // the cut planning itself (cut_kernel in sizing mode), one launch over every candidate
         // and one copy back: the same deterministic kernel every pass then runs against the
         // arenas reserved here (a host plan would need each document's decoded arrays back)
@@ -1064,6 +1110,23 @@ dtgpu_status stage_device(dtgpu_decoded *dec, const dtgpu_batch_opts *opts, dtgp
                 B->n_rest = uint32_t(lst.size() - nb);
             }
         }
+    }
+    // late pipeline: the prep / plan lists of its two pipelines.  A split pass wins (it already
+    // runs a side pipeline on these streams; late_pipe_documents leaves no batch to both).
+    if (B->split) B->late_pipe = false;
+    if (B->late_pipe) {
+        std::vector<uint32_t> lst, late;
+        for (size_t i = 0; i < n; i++)
+            if (!B->ff_doc[i]) (B->late_doc[i] ? late : lst).push_back(uint32_t(i));
+        B->n_first = uint32_t(lst.size());
+        B->n_late = uint32_t(late.size());
+        append(lst, late);
+        CK(B->d_late.upload(lst, s));
+        CK(hipStreamSynchronize(s));
+        if (!B->ev_sw0) CK(hipEventCreateWithFlags(&B->ev_sw0, hipEventDisableTiming));
+        if (!B->ev_sw1) CK(hipEventCreateWithFlags(&B->ev_sw1, hipEventDisableTiming));
+        if (!B->ev_lprep) CK(hipEventCreateWithFlags(&B->ev_lprep, hipEventDisableTiming));
+        if (!B->ev_lgo) CK(hipEventCreateWithFlags(&B->ev_lgo, hipEventDisableTiming));
     }
     stage_prof("stage: split setup");
     *out = B.release();

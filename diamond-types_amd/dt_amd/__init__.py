@@ -131,6 +131,8 @@ def lib():
     L.dtgpu_batch_host_planned.restype = sz
     L.dtgpu_batch_fast_forwarded.argtypes = [vp, ctypes.POINTER(ctypes.c_uint8), sz]
     L.dtgpu_batch_fast_forwarded.restype = sz
+    L.dtgpu_batch_late_pipelined.argtypes = [vp, ctypes.POINTER(ctypes.c_uint8), sz]
+    L.dtgpu_batch_late_pipelined.restype = sz
     pu32 = ctypes.POINTER(ctypes.c_uint32)
     L.dtgpu_batch_plan.argtypes = [vp, sz, pu32, sz, pu32, sz, ctypes.POINTER(sz), ctypes.POINTER(sz)]
     L.dtgpu_oplog_ins_content.argtypes = [vp, ctypes.c_char_p, sz]
@@ -815,6 +817,14 @@ class Batch:
         n = len(self)
         buf = (ctypes.c_uint8 * max(1, n))()
         lib().dtgpu_batch_fast_forwarded(self._h, buf, n)
+        return [int(x) for x in buf[:n]]
+
+    def late_pipelined(self):
+        """Per document: 1 when every pass runs it in the late pipeline (dtgpu_batch_late_pipelined),
+        else 0; all 0 when the batch runs one pipeline."""
+        n = len(self)
+        buf = (ctypes.c_uint8 * max(1, n))()
+        lib().dtgpu_batch_late_pipelined(self._h, buf, n)
         return [int(x) for x in buf[:n]]
 
     def plan(self, i):

@@ -272,7 +272,8 @@ size_t dtgpu_batch_size(const dtgpu_batch *batch);
  * host-staged batches), milliseconds.  In a split pass (a skewed device-staged batch whose
  * biggest LDS tier runs its own prep -> plan -> replay on a side stream) out[2] and out[0] are
  * the main pipeline's prep and plan; the big tier's prep and plan overlap them and are counted
- * inside out[1]. */
+ * inside out[1].  Likewise with the late pipeline (dtgpu_batch_late_pipelined): out[2] and out[0]
+ * are the first round's prep and plan, the late documents' share is inside out[1]. */
 dtgpu_status dtgpu_batch_last_times(const dtgpu_batch *batch, float out[3]);
 /* Documents planned on the host because the device planner declined them: returns their count
  * and, when flags is not NULL, one code per document: 0 device-planned, 1 DTGPU_HOST_PLAN set,
@@ -285,6 +286,12 @@ size_t dtgpu_batch_host_planned(const dtgpu_batch *batch, uint8_t *flags, size_t
  * the device a piece table of segment replays composed pairwise, not the per-item tracker.
  * flags[i] = 1 for those documents (up to cap); returns how many there are. */
 size_t dtgpu_batch_fast_forwarded(const dtgpu_batch *batch, uint8_t *flags, size_t cap);
+/* Documents of a device-staged batch that every pass prepares, plans and replays in the late
+ * pipeline: the smallest LDS tier's documents past its first resident round, on
+ * side streams, so that the first round's replay does not wait for them.  flags[i] = 1 for those documents (up to cap); returns how many there
+ * are, 0 when the batch runs one pipeline (DTGPU_LATE_PIPE=0, a split pass, a host-staged batch, a
+ * tier of one round or of many). */
+size_t dtgpu_batch_late_pipelined(const dtgpu_batch *batch, uint8_t *flags, size_t cap);
 /* The command stream of document `doc` as last planned (16-byte commands as uint32 quads
  * {op, lv, len, pos}; TOG commands index the retreat/advance entries copied to tlist).
  * NULL buffers query the sizes.  A fast-forwarded document (dtgpu_batch_fast_forwarded) has no
