@@ -118,6 +118,12 @@ extern "C" {
                             ignore_crc: c_int, ms: *mut f32, out: *mut *mut dtgpu_decoded) -> dtgpu_status;
     pub fn dtgpu_decode_add_result(merged: *const dtgpu_decoded, i: usize, frontier: *mut u64, cap: usize,
                                    n_frontier: *mut usize) -> dtgpu_status;
+    // ListOpLog::checkout(&[LV]) for a batch, up to the replay (oplog.rs:32-36)
+    pub fn dtgpu_decode_history(base: *const dtgpu_decoded, doc: *const u32, versions: *const u64,
+                                version_off: *const usize, n: usize, ms: *mut f32,
+                                out: *mut *mut dtgpu_decoded) -> dtgpu_status;
+    pub fn dtgpu_decode_history_result(hist: *const dtgpu_decoded, i: usize, frontier: *mut u64, cap: usize,
+                                       n_frontier: *mut usize) -> dtgpu_status;
     pub fn dtgpu_batch_create_decoded(dec: *mut dtgpu_decoded, out: *mut *mut dtgpu_batch) -> dtgpu_status;
     pub fn dtgpu_device_count() -> c_int;
     // the decoded oplog's arrays (op runs, inserted content, per-LV byte offsets, ...)

@@ -33,6 +33,10 @@ struct dtgpu_decoded {
     bool merged = false;
     std::vector<uint32_t> add_status;
     DevBuf<uint32_t> ffr;
+    // dtgpu_decode_run has run (a decoded handle's arrays exist); dtgpu_decode_history results:
+    // each output's request reduced to a frontier, in its base document's LVs
+    bool ran = false;
+    DevBuf<uint32_t> hfr;
     DevBuf<DecodeDesc> d_desc;
     DevBuf<DecodeResult> d_res;
     DecodeParams P{};

@@ -17,6 +17,7 @@
 
 #include "../../include/dtgpu.h"
 #include "dt_decoded.hpp"
+#include "dt_history.hpp"
 #include "dt_host.hpp"
 
 using namespace dtgpu;
@@ -38,6 +39,12 @@ uint32_t multmodp_host(uint32_t a, uint32_t b) {
 }
 
 uint64_t align256(uint64_t x) { return (x + 255) & ~uint64_t(255); }
+
+// SoA bytes of one decoded document: 16 B per op run and agent run, 8 per entry (+4 per CSR slot),
+// 4 per parent, the inserted bytes and 4 per LV of content offsets
+uint64_t soa_bytes(const DecodeResult &r) {
+    return 16ull * (r.n_ops + r.n_aruns) + 12ull * r.n_entries + 4 + 4ull * r.n_parents + r.n_content + 4ull * r.n_lv;
+}
 
 // Process-wide pinned staging chunks for document uploads (allocated once, reused by every batch;
 // each upload ends with its stream synchronised, so the next one finds both chunks idle).
@@ -321,6 +328,7 @@ dtgpu_status dtgpu_decode_run(dtgpu_decoded *D, float *ms) {
     float t = 0;
     if (hipEventElapsedTime(&t, D->ev0, D->ev1) != hipSuccess) return DTGPU_ERR_HIP;
     D->last_ms = t;
+    D->ran = true;
     if (ms) *ms = t;
     return DTGPU_OK;
 }
@@ -495,6 +503,157 @@ dtgpu_status dtgpu_decode_add_result(const dtgpu_decoded *M, size_t i, uint64_t 
     return dtgpu_status(st);
 }
 
+// ListOpLog::checkout(&[LV]) for a batch, up to the replay (dt_history.hip): output i is the history
+// of a version of resident document doc[i] as an oplog of its own, in a new handle.  Staging: the
+// request CSR goes to HBM, the mark launch sizes every output (exact LVs and content bytes, upper
+// bounds for the run arrays), the arenas are laid out from its counts and the emit launch fills them.
+dtgpu_status dtgpu_decode_history(const dtgpu_decoded *B, const uint32_t *doc, const uint64_t *versions,
+                                  const size_t *version_off, size_t n, float *ms, dtgpu_decoded **out) {
+    if (!B || !out || (n && (!doc || !version_off))) return DTGPU_ERR_ARG;
+    if (!B->merged && !B->ran) return DTGPU_ERR_ARG;   // not decoded yet
+    for (size_t i = 0; i < n; i++)
+        if (doc[i] >= B->n || version_off[i + 1] < version_off[i]) return DTGPU_ERR_ARG;
+    const size_t n_req = n ? version_off[n] - version_off[0] : 0;
+    if (n_req && !versions) return DTGPU_ERR_ARG;
+    auto M = new dtgpu_decoded();
+    std::unique_ptr<dtgpu_decoded> guard(M);
+    M->device = B->device;
+    M->merged = true;
+#define CK(x) do { if (DTGPU_HIP_FAILED(x)) return DTGPU_ERR_HIP; } while (0)
+    CK(hipSetDevice(M->device));
+    CK(hipStreamCreateWithFlags(&M->stream, hipStreamNonBlocking));
+    CK(hipEventCreate(&M->ev0));
+    CK(hipEventCreate(&M->ev1));
+    struct Ev {
+        hipEvent_t e[2] = {nullptr, nullptr};
+        ~Ev() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+    } ev;
+    CK(hipEventCreate(&ev.e[0]));
+    CK(hipEventCreate(&ev.e[1]));
+    hipStream_t s = M->stream;
+    M->n = n;
+    M->desc.assign(n, DecodeDesc{});
+    M->res.assign(n, DecodeResult{});
+    // the mark words of an output live in LDS up to this many base entries, in its HBM scratch
+    // past it (DTGPU_HISTORY_LDS_ENTRIES lowers the limit; 0: always HBM)
+    uint32_t lds_cap = HIST_LDS_ENTRIES;
+    if (const char *e = getenv("DTGPU_HISTORY_LDS_ENTRIES")) lds_cap = uint32_t(std::min<unsigned long>(strtoul(e, nullptr, 10), HIST_LDS_ENTRIES));
+    std::vector<HistDesc> hd(n, HistDesc{});
+    std::vector<uint32_t> req(n_req);
+    uint64_t scr = 0;
+    uint32_t lds_entries = 0;
+    for (size_t i = 0; i < n; i++) {
+        const DecodeDesc &bd = B->desc[doc[i]];
+        const DecodeResult &br = B->res[doc[i]];
+        HistDesc &h = hd[i];
+        h.skip = br.status;
+        h.b_in = bd.in_off; h.b_arun = bd.arun_off; h.b_op = bd.op_off; h.b_ent = bd.ent_off; h.b_poff = bd.poff_off;
+        h.b_par = bd.par_off; h.b_content = bd.content_off; h.b_lv = bd.lv_off; h.b_agent = bd.agent_off;
+        if (br.status == 0) {
+            h.b_in_len = bd.in_len; h.b_n_aruns = br.n_aruns; h.b_n_ops = br.n_ops; h.b_n_ent = br.n_entries;
+            h.b_n_par = br.n_parents; h.b_n_content = br.n_content; h.b_n_agents = br.n_agents;
+            h.b_n_lv = uint32_t(std::min<uint64_t>(br.n_lv, 0xFFFFFFFFull)); h.b_complete = br.content_complete;
+        }
+        h.req_off = version_off[i] - version_off[0];
+        h.n_req = uint32_t(version_off[i + 1] - version_off[i]);
+        for (size_t k = version_off[i]; k < version_off[i + 1]; k++)
+            req[k - version_off[0]] = uint32_t(std::min<uint64_t>(versions[k], 0xFFFFFFFFull));
+        h.use_lds = h.b_n_ent <= lds_cap ? 1u : 0u;
+        if (h.use_lds && !h.skip) lds_entries = std::max(lds_entries, h.b_n_ent);
+        h.scr_off = scr;
+        scr += uint64_t(HIST_ENT_WORDS) * h.b_n_ent;
+        h.o_ver = uint64_t(DECODE_MAX_FRONTIER) * i;
+    }
+    DevBuf<uint32_t> d_req, d_scr;
+    DevBuf<HistDesc> d_hd;
+    CK(d_req.upload(req, s));
+    CK(d_scr.alloc(scr));
+    CK(d_hd.upload(hd, s));
+    CK(M->d_res.alloc(n));
+    CK(M->ver.alloc(uint64_t(DECODE_MAX_FRONTIER) * n));
+    CK(M->hfr.alloc(uint64_t(DECODE_MAX_FRONTIER) * n));
+    HistParams H{};
+    H.b_in = B->in.p; H.b_content = B->content.p; H.b_aruns = B->aruns.p; H.b_ops = B->ops.p; H.b_ent = B->ent.p;
+    H.b_poff = B->poff.p; H.b_par = B->par.p; H.b_cbyte = B->cbyte.p; H.b_agents = B->agents.p;
+    H.req = d_req.p; H.scr = d_scr.p; H.o_ver = M->ver.p; H.o_front = M->hfr.p;
+    H.docs = d_hd.p; H.results = M->d_res.p; H.n_docs = uint32_t(n); H.lds_entries = lds_entries;
+    CK(hipEventRecord(M->ev0, s));
+    if (launch_hist_mark(H, s)) return DTGPU_ERR_HIP;
+    CK(hipEventRecord(M->ev1, s));
+    if (n) CK(hipMemcpyAsync(M->res.data(), M->d_res.p, n * sizeof(DecodeResult), hipMemcpyDeviceToHost, s));
+    CK(hipStreamSynchronize(s));
+    // the output arenas, from the mark launch's counts
+    uint64_t in = 0, ar = 0, ops = 0, ent = 0, poff = 0, par = 0, content = 0, lv = 0, ag = 0;
+    for (size_t i = 0; i < n; i++) {
+        const DecodeResult &r = M->res[i];
+        HistDesc &h = hd[i];
+        DecodeDesc &md = M->desc[i];
+        if (r.status) h.skip = r.status;
+        const bool ok = h.skip == 0;
+        h.c_arun = ok ? r.n_aruns : 0; h.c_op = ok ? r.n_ops : 0; h.c_ent = ok ? r.n_entries : 0; h.c_par = ok ? r.n_parents : 0;
+        h.c_content = ok ? r.n_content : 0; h.c_lv = ok ? uint32_t(r.n_lv) : 0; h.c_agent = ok ? h.b_n_agents : 0;
+        h.c_in = ok ? h.b_in_len : 0;
+        h.o_in = in; in = align256(in + h.c_in + 256);
+        h.o_arun = ar; ar += h.c_arun;
+        h.o_op = ops; ops += h.c_op;
+        h.o_ent = ent; ent += h.c_ent;
+        h.o_poff = poff; poff += h.c_ent + 1;
+        h.o_par = par; par += h.c_par;
+        h.o_content = content; content += h.c_content;
+        h.o_lv = lv; lv += h.c_lv;
+        h.o_agent = ag; ag += h.c_agent;
+        md.in_off = h.o_in; md.in_len = h.c_in;
+        md.arun_off = h.o_arun; md.op_off = h.o_op; md.ent_off = h.o_ent; md.poff_off = h.o_poff; md.par_off = h.o_par;
+        md.content_off = h.o_content; md.lv_off = h.o_lv; md.agent_off = h.o_agent; md.ver_off = h.o_ver;
+        md.arun_cap = h.c_arun; md.op_cap = h.c_op; md.ent_cap = h.c_ent; md.par_cap = h.c_par;
+        md.content_cap = h.c_content; md.lv_cap = h.c_lv; md.agent_cap = h.c_agent;
+    }
+    CK(M->in.alloc(in)); CK(M->aruns.alloc(4 * ar)); CK(M->ops.alloc(4 * ops)); CK(M->ent.alloc(2 * ent));
+    CK(M->poff.alloc(poff)); CK(M->par.alloc(par)); CK(M->content.alloc(content)); CK(M->cbyte.alloc(lv));
+    CK(M->agents.alloc(2 * ag));
+    CK(hipMemsetAsync(M->in.p, 0, std::max<uint64_t>(in, 1), s));
+    CK(d_hd.upload(hd, s));
+    H.docs = d_hd.p;
+    H.o_in = M->in.p; H.o_content = M->content.p; H.o_aruns = M->aruns.p; H.o_ops = M->ops.p; H.o_ent = M->ent.p;
+    H.o_poff = M->poff.p; H.o_par = M->par.p; H.o_cbyte = M->cbyte.p; H.o_agents = M->agents.p;
+    CK(hipEventRecord(ev.e[0], s));
+    if (launch_hist_emit(H, s)) return DTGPU_ERR_HIP;
+    CK(hipEventRecord(ev.e[1], s));
+    if (n) CK(hipMemcpyAsync(M->res.data(), M->d_res.p, n * sizeof(DecodeResult), hipMemcpyDeviceToHost, s));
+    CK(hipStreamSynchronize(s));
+    float t0 = 0, t1 = 0;
+    CK(hipEventElapsedTime(&t0, M->ev0, M->ev1));
+    CK(hipEventElapsedTime(&t1, ev.e[0], ev.e[1]));
+#undef CK
+    M->last_ms = t0 + t1;
+    if (ms) *ms = t0 + t1;
+    M->add_status.assign(n, 0);
+    for (size_t i = 0; i < n; i++) {
+        DecodeResult &r = M->res[i];
+        if (r.status == 0) M->in_bytes += soa_bytes(B->res[doc[i]]);   // read: the base document's arrays
+        r.prof[1] = uint32_t(t0 * 1000.f);   // the launches' microseconds, with the mark form in prof[0]
+        r.prof[2] = uint32_t(t1 * 1000.f);
+        M->add_status[i] = r.status;
+    }
+    *out = guard.release();
+    return DTGPU_OK;
+}
+
+dtgpu_status dtgpu_decode_history_result(const dtgpu_decoded *H, size_t i, uint64_t *frontier, size_t cap,
+                                         size_t *n_frontier) {
+    if (!H || !H->hfr.p || i >= H->n || (!frontier && cap)) return DTGPU_ERR_ARG;
+    const uint32_t st = H->res[i].status;
+    const size_t k = st == 0 ? H->res[i].n_version : 0;
+    if (n_frontier) *n_frontier = k;
+    if (k && cap) {
+        std::vector<uint32_t> f(k);
+        if (hipMemcpy(f.data(), H->hfr.p + H->desc[i].ver_off, k * 4, hipMemcpyDeviceToHost) != hipSuccess)
+            return DTGPU_ERR_HIP;
+        for (size_t j = 0; j < k && j < cap; j++) frontier[j] = f[j];
+    }
+    return dtgpu_status(st);
+}
+
 size_t dtgpu_decode_size(const dtgpu_decoded *D) { return D ? D->n : 0; }
 
 dtgpu_status dtgpu_decode_status(const dtgpu_decoded *D, size_t i, uint64_t out[12]) {
@@ -562,14 +721,9 @@ size_t dtgpu_decode_export(const dtgpu_decoded *D, size_t i, int what, void *out
 uint64_t dtgpu_decode_bytes(const dtgpu_decoded *D, int which) {
     if (!D) return 0;
     if (which == 0) return D->in_bytes;
-    // SoA written: 16 B per op run and agent run, 8 per entry (+4 per CSR slot), 4 per parent,
-    // the inserted bytes and 4 per LV of content offsets
-    uint64_t b = 0;
-    for (size_t i = 0; i < D->n; i++) {
-        const DecodeResult &r = D->res[i];
-        if (r.status) continue;
-        b += 16ull * (r.n_ops + r.n_aruns) + 12ull * r.n_entries + 4 + 4ull * r.n_parents + r.n_content + 4ull * r.n_lv;
-    }
+    uint64_t b = 0;   // SoA written
+    for (size_t i = 0; i < D->n; i++)
+        if (D->res[i].status == 0) b += soa_bytes(D->res[i]);
     return b;
 }
 

@@ -223,6 +223,9 @@ def lib():
     L.dtgpu_decode_add.argtypes = [vp, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(sz), sz, c,
                                    ctypes.POINTER(ctypes.c_float), ctypes.POINTER(vp)]
     L.dtgpu_decode_add_result.argtypes = [vp, sz, pu64, sz, ctypes.POINTER(sz)]
+    L.dtgpu_decode_history.argtypes = [vp, ctypes.POINTER(ctypes.c_uint32), pu64, ctypes.POINTER(sz), sz,
+                                       ctypes.POINTER(ctypes.c_float), ctypes.POINTER(vp)]
+    L.dtgpu_decode_history_result.argtypes = [vp, sz, pu64, sz, ctypes.POINTER(sz)]
     L.dtgpu_batch_create_decoded.argtypes = [vp, ctypes.POINTER(vp)]
     L.dtgpu_graph_queries.argtypes = [ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(sz), sz,
                                       ctypes.POINTER(GraphQuery), sz, ctypes.POINTER(ctypes.c_int64), sz,
@@ -936,6 +939,59 @@ class DecodeBatch:
         buf = (ctypes.c_uint64 * 64)()
         st = lib().dtgpu_decode_add_result(self._h, i, buf, 64, ctypes.byref(k))
         return st, list(buf[:k.value])
+
+    def history(self, docs, versions):
+        """ListOpLog::checkout(&[LV]) up to the replay, batched on the GPU (dtgpu_decode_history):
+        a new DecodeBatch whose oplog i is the history of versions[i] (any set of LVs; [] is ROOT)
+        of document docs[i] of this one (unchanged).  Per-output outcome: history_result(i)."""
+        n = len(docs)
+        if len(versions) != n:
+            raise ValueError("one version per document index")
+        flat, off = [], [0]
+        for v in versions:
+            flat.extend(int(x) for x in v)
+            off.append(len(flat))
+        d = (ctypes.c_uint32 * max(n, 1))(*[int(x) for x in docs])
+        pv, _ = _u64s(flat)
+        po = (ctypes.c_size_t * (n + 1))(*off)
+        ms = ctypes.c_float()
+        h = ctypes.c_void_p()
+        _check(lib().dtgpu_decode_history(self._h, d, pv, po, n, ctypes.byref(ms), ctypes.byref(h)))
+        m = DecodeBatch.__new__(DecodeBatch)
+        m._h, m.n, m._keep, m.last_ms = h, n, None, ms.value
+        return m
+
+    def history_result(self, i):
+        """(status, the request reduced to a frontier in the base document's LVs) of output i of a
+        history batch."""
+        k = ctypes.c_size_t()
+        buf = (ctypes.c_uint64 * 64)()
+        st = lib().dtgpu_decode_history_result(self._h, i, buf, 64, ctypes.byref(k))
+        return st, list(buf[:k.value])
+
+    def checkout_versions(self, docs, versions):
+        """ListOpLog::checkout(versions[i]) of document docs[i] for a whole batch: the histories
+        projected on the GPU (history), then one device-staged checkout batch.  Returns the
+        ListBranch of every request (content, and the frontier in the base document's LVs); an
+        output whose projection or checkout fails raises ParseError.  (ROOT requests are the empty
+        branch: they are answered here, a zero-LV oplog is not staged.)"""
+        live = [i for i, v in enumerate(versions) if len(v)]
+        out = [ListBranch() for _ in versions]
+        if not live:
+            return out
+        h = self.history([docs[i] for i in live], [versions[i] for i in live])
+        fronts = []
+        for k in range(len(live)):
+            st, f = h.history_result(k)
+            _check(st)
+            fronts.append(f)
+        b = h.checkout_batch()
+        b.run()
+        b.sync()
+        for k, (i, r) in enumerate(zip(live, b.results())):
+            _check(r["status"])
+            out[i] = ListBranch(b.text(k), fronts[k])
+        return out
 
     def checkout_batch(self):
         """A device-staged checkout Batch over these decoded (or merged) oplogs; consumes this

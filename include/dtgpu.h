@@ -441,6 +441,30 @@ dtgpu_status dtgpu_decode_add(const dtgpu_decoded *base, const uint8_t *const *p
                               size_t n, int ignore_crc, float *ms, dtgpu_decoded **out);
 dtgpu_status dtgpu_decode_add_result(const dtgpu_decoded *merged, size_t i, uint64_t *frontier, size_t cap,
                                      size_t *n_frontier);
+/* ListOpLog::checkout(&[LV]) (src/list/oplog.rs:32-36; ListBranch::new_at_local_version) for a
+ * batch, up to the replay: output i is the history of versions[version_off[i] .. version_off[i+1])
+ * of resident document doc[i] as an oplog of its own (compacted LVs; agents, seqs and positions
+ * unchanged), built on the GPU by one wavefront per output (dt_history.hip) into a new handle.
+ * `base` (after dtgpu_decode_run, a dtgpu_decode_add result or a history handle) is unchanged;
+ * doc[i] may repeat, in any order (DTGPU_ERR_ARG when one is >= dtgpu_decode_size(base)).  A
+ * request is any set of the document's LVs -- unsorted, with duplicates, not a frontier; the empty
+ * request is ROOT.  For every output with status 0 the dtgpu_decode_export arrays equal
+ * dtgpu_oplog_export of dtgpu_oplog_history(document, version), element for element.  Per-output
+ * status: the base document's own when that is not 0; DTGPU_ERR_ARG for an LV >= the document's
+ * LV count; DTGPU_DECODE_DEFER when the reduced frontier is wider than 64; DTGPU_ERR_CAPACITY when
+ * an arena reservation proves too small.  A failed output never fails the batch.  The new handle
+ * behaves as a dtgpu_decode_add result: it exports, checks out with dtgpu_batch_create_decoded, is
+ * a base for dtgpu_decode_add and dtgpu_decode_history, and cannot be re-decoded.  *ms = the two
+ * projection kernels' time.  dtgpu_decode_bytes(hist, 0) is the base SoA bytes read, (hist, 1) the
+ * SoA bytes written; dtgpu_decode_profile(hist, i) gives out[0] = 1 when the per-entry mark words
+ * were kept in LDS, 2 in HBM scratch (entries past 12288, or past DTGPU_HISTORY_LDS_ENTRIES when
+ * that is set in the environment at call time), out[1], out[2] = the mark and emit launches' us. */
+dtgpu_status dtgpu_decode_history(const dtgpu_decoded *base, const uint32_t *doc, const uint64_t *versions,
+                                  const size_t *version_off, size_t n, float *ms, dtgpu_decoded **out);
+/* Output i's status, and its request reduced to a frontier (find_dominators), in the base
+ * document's LVs, ascending. */
+dtgpu_status dtgpu_decode_history_result(const dtgpu_decoded *hist, size_t i, uint64_t *frontier, size_t cap,
+                                         size_t *n_frontier);
 /* A device-staged checkout batch over a decoded handle (consumed, also on failure): decoded here
  * unless it already holds merged oplogs; then as dtgpu_batch_create_device. */
 dtgpu_status dtgpu_batch_create_decoded(dtgpu_decoded *dec, dtgpu_batch **out);
