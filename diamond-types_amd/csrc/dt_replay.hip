@@ -1152,6 +1152,116 @@ DEV void toggle_pass(Doc &D, uint32_t off, uint32_t n, uint32_t pre, bool have_p
     wave_fence();
 }
 
+// The same pass for n <= 64 entries (every pass of a friendsforever document: 14 entries on
+// average, 49 at most), as straight-line code: one chunk, so no chunk loop with its carried
+// entries, no next-chunk targets, one failure ballot; and the delete targets are loaded and the
+// duplicate lanes merged only when the pass holds a delete entry at all (only a deleted item can
+// be touched twice).  Leaves the state toggle_pass leaves: pc[], the packed counts with their
+// DIRTY bits, the chunk / superblock totals and D.cb.
+template <int L, bool PROF>
+DEV void toggle_pass_1(Doc &D, uint32_t off, uint32_t n, uint32_t pre, bool have_pre) {
+    const uint32_t l = lane_id();
+    uint64_t tq = tick<PROF>();
+    if (n == 0) return;
+    const uint32_t e = have_pre ? pre : D.tlist[off + min(l, n - 1)];
+    const bool valid = l < n;
+    const uint32_t lv = e & 0x3FFFFFFFu;
+    uint32_t item = lv;
+    int32_t d = int32_t((e >> 31) << 1) - 1;   // net delta (+1 advance, -1 retreat)
+    int32_t dneg = int32_t(e >> 31) - 1;       // sum of the retreats (applied first)
+    bool act = valid && lv < D.n_lv;
+    bool bad = valid && lv >= D.n_lv;
+    const u64 dmask0 = BALLOT(act && ((e >> 30) & 1u));
+    if (dmask0) {   // delete entries: their targets, then the lanes that share an item
+        const bool del = (dmask0 >> l) & 1ull;
+        const uint32_t tgt = *reinterpret_cast<const uint32_t *>(D.ao + (del ? lv : 0u));
+        item = del ? tgt : lv;
+        bad = bad || (del && tgt >= D.n_lv);
+        act = act && !(del && tgt >= D.n_lv);
+        const u64 dmask = BALLOT(act && del);
+        bool dup = del;
+        if (__popcll(dmask) > 4) {   // (toggle_pass: 63 lane rotations beat the merge loop from here)
+            dup = false;
+            const uint32_t x = act ? item : (0x80000000u | l);   // inactive lanes never match
+            uint32_t r0 = x, r1 = shfl(x, (l + 16) & 63u), r2 = shfl(x, (l + 32) & 63u), r3 = shfl(x, (l + 48) & 63u);
+            uint32_t mn = min(min(r1 ^ x, r2 ^ x), r3 ^ x);
+#pragma unroll
+            for (int k = 1; k < 16; k++) {
+                r0 = uint32_t(__builtin_amdgcn_mov_dpp(int(r0), 0x13C, 0xF, 0xF, false));   // wave_ror:1
+                r1 = uint32_t(__builtin_amdgcn_mov_dpp(int(r1), 0x13C, 0xF, 0xF, false));
+                r2 = uint32_t(__builtin_amdgcn_mov_dpp(int(r2), 0x13C, 0xF, 0xF, false));
+                r3 = uint32_t(__builtin_amdgcn_mov_dpp(int(r3), 0x13C, 0xF, 0xF, false));
+                mn = min(mn, min(min(r0 ^ x, r1 ^ x), min(r2 ^ x, r3 ^ x)));
+            }
+            dup = mn == 0u;
+        }
+        for (u64 dm = BALLOT(act && dup); dm;) {   // each round retires >= 1 lane
+            const uint32_t t = bcast(item, first_lane(dm));
+            const u64 same = BALLOT(act && item == t);
+            if (__popcll(same) > 1) {
+                const bool mine = (same >> l) & 1ull;
+                const int32_t sum = int32_t(wave_sum(mine ? uint32_t(d) : 0u));
+                const int32_t neg = int32_t(wave_sum(mine ? uint32_t(dneg) : 0u));
+                if (mine) {
+                    if (l == first_lane(same)) { d = sum; dneg = neg; }
+                    else act = false;
+                }
+            }
+            dm &= ~same;
+        }
+    }
+    if (PROF) { const uint64_t t = tick<PROF>(); D.prof[P_T1] += t - tq; tq = t; }
+    // every lane loads (inactive ones item 0's word); only the store is masked
+    const uint32_t w = ld(D.pc + (act ? item : 0u));
+    const uint32_t bw = pc_blk(w), oc = pc_cnt(w), nc = oc + uint32_t(d);
+    // oc + dneg < 0, oc + d > 0xFFFF or a block past the count: one sign test
+    const bool badc = act && int32_t((oc + uint32_t(dneg)) | (0xFFFFu - nc) | (D.nb - 1u - bw)) < 0;
+    const bool ok = act && !badc;
+    if (ok) st(D.pc + item, pc_of(bw, nc));
+    if (BALLOT(bad || badc)) { fail(D, ErrCheckout, 16); return; }
+    const uint32_t b = ok ? bw : 0u;
+    const bool fv = ok && ((oc == 1) != (nc == 1));
+    const bool fl = ok && ((oc != 0) != (nc != 0));
+    const int32_t dv = fv ? (nc == 1 ? 1 : -1) : 0;
+    const int32_t dl = fl ? (nc != 0 ? 1 : -1) : 0;
+    const bool flip = fv || fl;
+    if (BALLOT(flip && b == D.cb)) D.cb = NONE;
+    if (PROF) { const uint64_t t = tick<PROF>(); D.prof[P_T2] += t - tq; tq = t; }
+    if (L == IX_FLAT) {   // flat LDS index: the chunk's packed totals in one atomic
+        if (flip) {
+            at_add(D.top + (uint32_t(D.opos16[b]) >> 6), uint32_t(dv) + (uint32_t(dl) << 16));
+            at_add(D.cnt + b, uint32_t(dv) * C_VIS + uint32_t(dl) * C_LIVE);
+            at_or(D.cnt + b, C_DIRTY);
+        }
+    } else if (L) {   // LDS index: per-lane LDS atomics
+        if (flip) {
+            const uint32_t tp = ix<L>(D.sbpos + (opos_of<L>(D, b) >> 6));
+            if (fv) at_add(D.top + tp, uint32_t(dv));
+            if (fl) at_add(D.tlive + tp, uint32_t(dl));
+            at_add(D.cnt + b, uint32_t(dv) * C_VIS + uint32_t(dl) * C_LIVE);
+            at_or(D.cnt + b, C_DIRTY);
+        }
+    } else {   // HBM index: one atomic per distinct block (a global atomic is a memory-side request)
+        for (u64 pend = BALLOT(flip); pend;) {   // each round retires >= 1 lane
+            const uint32_t f = first_lane(pend);
+            const uint32_t bb = bcast(b, f);
+            const u64 same = BALLOT(flip && b == bb);
+            const bool mine = (same >> l) & 1ull;
+            const uint32_t sv = wave_sum(mine ? uint32_t(dv) : 0u), sl = wave_sum(mine ? uint32_t(dl) : 0u);
+            if (l == f) {
+                const uint32_t tp = ix<L>(D.sbpos + (opos_of<L>(D, bb) >> 6));
+                if (sv) at_add(D.top + tp, sv);
+                if (sl) at_add(D.tlive + tp, sl);
+                at_add(D.cnt + bb, sv * C_VIS + sl * C_LIVE);
+                at_or(D.cnt + bb, C_DIRTY);
+            }
+            pend &= ~same;
+        }
+    }
+    if (PROF) { const uint64_t t = tick<PROF>(); D.prof[P_T3] += t - tq; tq = t; }
+    wave_fence();
+}
+
 // Multi-wave retreat / advance pass (the big LDS tiers' workgroups have TOG_WAVES waves; the
 // first replays, the others wait at a barrier until a long pass is posted).  The counters make
 // the pass order-free (see toggle_pass), so the waves take 64-entry chunks round robin and
@@ -1625,6 +1735,7 @@ DEV void run_doc(Doc &D) {
                 if (PROF) D.prof[P_DEL] += tick<PROF>() - t0;
             } else {
                 if (MW && n >= TOG_MW_MIN) toggle_mw<L>(D, a, n);
+                else if (n <= 64) toggle_pass_1<L, PROF>(D, a, n, pf, pf_ok);
                 else toggle_pass<L, PROF>(D, a, n, pf, pf_ok);
                 if (PROF) D.prof[P_TOG] += tick<PROF>() - t0;
             }
