@@ -32,9 +32,11 @@
 
 #include "dt_decode.hpp"
 #include "dt_device.hpp"
+#include "dt_wave.hpp"
 
 namespace dtgpu {
 namespace ddec {
+using namespace wave;
 
 enum : int {
     S_OK = 0, InvalidMagic = 1, UnsupportedProtocolVersion = 2, DocIdMismatch = 3, BaseVersionUnknown = 4, UnknownChunk = 5,
@@ -45,52 +47,7 @@ enum : int {
 
 #define TRY(x) do { const int s_ = (x); if (s_) return s_; } while (0)
 
-constexpr uint32_t CRC_POLY = 0x82F63B78u;
 constexpr uint64_t LIM31 = 1ull << 31;
-
-__device__ __forceinline__ uint32_t lane() { return __lane_id(); }
-__device__ __forceinline__ uint32_t rdl(uint32_t v, uint32_t l) {
-    return uint32_t(__builtin_amdgcn_readlane(int(v), int(l)));
-}
-__device__ __forceinline__ uint64_t ballot(bool p) { return __ballot(p); }
-__device__ __forceinline__ uint64_t lt_mask() { return (1ull << lane()) - 1ull; }
-__device__ __forceinline__ uint32_t popc(uint64_t m) { return uint32_t(__popcll(m)); }
-__device__ __forceinline__ uint32_t ctz(uint64_t m) { return uint32_t(__ffsll((unsigned long long)m) - 1); }
-// Inclusive prefix sum over the wave (all lanes active): row_shr 1, 2, 4, 8 scan each row of 16
-// lanes, row_bcast 15 adds row 0's total to row 1 and row 2's to row 3, row_bcast 31 adds rows
-// 0-1's total to rows 2 and 3 -- six DPP adds instead of six dependent LDS permutes.
-__device__ __forceinline__ uint32_t scan_incl(uint32_t v) {
-    v += uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x111, 0xf, 0xf, false));   // row_shr:1
-    v += uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x112, 0xf, 0xf, false));   // row_shr:2
-    v += uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x114, 0xf, 0xf, false));   // row_shr:4
-    v += uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x118, 0xf, 0xf, false));   // row_shr:8
-    v += uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x142, 0xa, 0xf, false));   // row_bcast:15
-    v += uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x143, 0xc, 0xf, false));   // row_bcast:31
-    return v;
-}
-// Prefix composition of boolean functions f_l: {0,1} -> {0,1} along the wave (all lanes
-// active), each packed as f(0) | !f(1) << 1 so that the identity is 0 (what a DPP lane without a
-// source reads): lane l gets f_l o ... o f_0, by the same row scan and row broadcasts as scan_incl.
-__device__ __forceinline__ uint32_t fn_pack(bool f0, bool f1) { return uint32_t(f0) | (uint32_t(!f1) << 1); }
-__device__ __forceinline__ uint32_t compose_scan(uint32_t v) {
-    auto step = [&](uint32_t p) {   // v := v o p
-        const uint32_t m0 = v & 1u, m1 = ((v >> 1) & 1u) ^ 1u;
-        const uint32_t p0 = p & 1u, p1 = ((p >> 1) & 1u) ^ 1u;
-        v = (p0 ? m1 : m0) | (((p1 ? m1 : m0) ^ 1u) << 1);
-    };
-    step(uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x111, 0xf, 0xf, false)));   // row_shr:1
-    step(uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x112, 0xf, 0xf, false)));   // row_shr:2
-    step(uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x114, 0xf, 0xf, false)));   // row_shr:4
-    step(uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x118, 0xf, 0xf, false)));   // row_shr:8
-    step(uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x142, 0xa, 0xf, false)));   // row_bcast:15
-    step(uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x143, 0xc, 0xf, false)));   // row_bcast:31
-    return v;
-}
-// LDS stores of this wave become visible to its lanes' later LDS loads (a wave's LDS operations
-// complete in order; this only keeps the compiler from reordering them).
-__device__ __forceinline__ void wave_lds_fence() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); }
-// Stores of this wave become visible to its later loads (same CU; workgroup scope).
-__device__ __forceinline__ void wave_fence() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); }
 
 // ---------------------------------------------------------------------------------------------
 // byte windows and readers
@@ -435,29 +392,6 @@ struct Quads {
     __device__ uint64_t count() const { return at + n; }
 };
 
-// CRC-32C combine (zlib's crc32_combine scheme over the reflected polynomial)
-__device__ __forceinline__ uint32_t multmodp(uint32_t a, uint32_t b) {
-    if (!a) return 0;
-    uint32_t m = 1u << 31, p = 0;
-    for (;;) {
-        if (a & m) {
-            p ^= b;
-            if ((a & (m - 1)) == 0) break;
-        }
-        m >>= 1;
-        b = (b & 1u) ? (b >> 1) ^ CRC_POLY : b >> 1;
-    }
-    return p;
-}
-__device__ __forceinline__ uint32_t x2nmodp(const uint32_t *x2n, uint64_t n, uint32_t k) {
-    uint32_t p = 1u << 31;
-    while (n) {
-        if (n & 1) p = multmodp(x2n[k & 31], p);
-        n >>= 1;
-        k++;
-    }
-    return p;
-}
 // CRC-32C of s[0, n): 64 lane segments (4-B aligned), merged in order.
 __device__ __forceinline__ uint32_t crc32c_par(const uint8_t *s, uint32_t n, const uint32_t *T, const uint32_t *x2n) {
     // segments of a multiple of 16 bytes (s is 256-B aligned): 16-byte loads, a quarter of the
@@ -655,16 +589,16 @@ __device__ __forceinline__ bool lz4_block(Ctx &C, const Rd &src, uint8_t *dst, u
         const bool mapped = nw <= 64u;   // uniform
         if (mapped) {
             if (lane() < nw) lzm[lane()] = make_uint4(0u, 0u, 0u, 0u);
-            wave_lds_fence();
+            fence_wave_nobarrier();
             const uint32_t rel = so - bs;
             if (lane() < ns && rel < op - bs)
                 atomicOr(reinterpret_cast<uint32_t *>(&lzm[rel >> 6]) + ((rel >> 5) & 1u), 1u << (rel & 31u));
-            wave_lds_fence();
+            fence_wave_nobarrier();
             const uint4 wv = lzm[lane()];
             const uint32_t c = lane() < nw ? uint32_t(__popc(wv.x) + __popc(wv.y)) : 0u;
             const uint32_t inc = scan_incl(c);
             if (lane() < nw) lzm[lane()].z = inc - c;
-            wave_lds_fence();
+            fence_wave_nobarrier();
         }
         constexpr uint32_t CU = THREE ? 16 : 8;
         bool waited = wflag == nullptr;   // THREE, odd batches: wait for the even batch's stores
@@ -715,7 +649,7 @@ __device__ __forceinline__ bool lz4_block(Ctx &C, const Rd &src, uint8_t *dst, u
                 fr[u] = from;
                 inm |= uint32_t(inp) << u;
                 if (ring && p < op) lzr[p & (ring_n - 1u)] = from | (uint32_t(inp) << 31);
-                wave_lds_fence();
+                fence_wave_nobarrier();
             }
             if (!waited) {   // (the first group's sources are resolved while the other copier works)
                 for (uint32_t it = 0; *wflag < wval; it++) {
@@ -733,7 +667,7 @@ __device__ __forceinline__ bool lz4_block(Ctx &C, const Rd &src, uint8_t *dst, u
             for (uint32_t u = 0; u < CU; u++)
                 if (g0 + 64u * u + lane() < op) dst[g0 + 64u * u + lane()] = uint8_t(v[u]);
         }
-        wave_fence();   // the next batch reads these bytes
+        fence_workgroup();   // the next batch reads these bytes
     };
     if (!TWO) {
         while (!end) {
@@ -960,7 +894,7 @@ __device__ __forceinline__ int build_lookup(const Out &O, const Lds &L, uint32_t
             __syncthreads();
         }
     }
-    wave_fence();
+    fence_workgroup();
     // an entry below its predecessor's end clears its agent's monotone flag
     for (uint32_t a = 0; a < n_agents; a++) {
         const uint32_t off = L.aoff[a], cnt = L.acnt[a];
@@ -1706,7 +1640,7 @@ __device__ __forceinline__ FastOut fast_runs(VQ qav, VQ qtp, VQ runs, uint32_t t
         }
     }
     if ((nb & 63u) && lane() < (nb & 63u)) bnd[(nb & ~63u) + lane()] = bbuf;
-    wave_fence();
+    fence_workgroup();
     fo.t_mid = __builtin_amdgcn_s_memtime();
     uint32_t bblk = 0xFFFFFFFFu, bcache = 0, bi = 0;
     const uint32_t total = uint32_t(next_assign);
@@ -2251,7 +2185,7 @@ __device__ __forceinline__ int decode_doc(const DecodeParams &P, const DecodeDes
     qa.flush(O.aruns);
     qp.flush(O.pre);
     const uint32_t n_aruns = uint32_t(qa.at), n_pre = uint32_t(qp.at);
-    wave_fence();
+    fence_workgroup();
     prof_mark(2);
     TRY(build_lookup(O, L, n_agents, n_aruns));
     prof_mark(3);
@@ -2367,7 +2301,7 @@ __device__ __forceinline__ int decode_doc(const DecodeParams &P, const DecodeDes
             if (crc32c_par(C.in, len - reader_len, L.crc, P.x2n) != want) return ChecksumFailed;
         }
     }
-    wave_fence();
+    fence_workgroup();
     prof_mark(5);
 
     // ---- the insert text (every known piece, in order) ------------------------------------------
@@ -2401,7 +2335,7 @@ __device__ __forceinline__ int decode_doc(const DecodeParams &P, const DecodeDes
     // ---- split op runs at graph-entry boundaries (HostOpLog::finish) --------------------------
     // one run per lane: its first entry by bisection, its pieces (one per entry it touches) at a
     // prefix-sum offset; a run rarely spans entries, so the per-lane loops are short
-    wave_fence();   // the entries were written by lane 0 above
+    fence_workgroup();   // the entries were written by lane 0 above
     {
         uint32_t nout = 0, ebase = 0;   // ebase: the entry of the previous chunk's last run
         for (uint32_t b0 = 0; b0 < n_pre; b0 += 64) {
@@ -2692,7 +2626,7 @@ __device__ __forceinline__ int add_doc(const AddParams &P, const AddDesc &D, Dec
     // filter's new pieces), and a known one usually from the 64 runs around its last hit.
     uint32_t *A_end = L.acnt, *A_mono = L.amono, *A_cur = L.acur;
     auto seq_find = [&](uint32_t a, uint64_t seq, uint64_t &lv, uint64_t &gap) -> bool {
-        if (dirty) { wave_fence(); dirty = false; }
+        if (dirty) { fence_workgroup(); dirty = false; }
         gap = ~uint64_t(0);
         const bool mono = A_mono[a] != 0;
         if (mono) {
@@ -2896,7 +2830,7 @@ __device__ __forceinline__ int add_doc(const AddParams &P, const AddDesc &D, Dec
                 if (n_agents >= D.c_agent) return ErrCapacity;
                 id = n_agents++;
                 if (lane() == 0) M.agents[id] = make_uint2(D.p_rel + noff, nlen);
-                wave_fence();
+                fence_workgroup();
             }
             if (lane() == 0) { L.fmap[n_file] = id; L.fseq[n_file] = 0; }
             n_file++;
@@ -3147,7 +3081,7 @@ __device__ __forceinline__ int add_doc(const AddParams &P, const AddDesc &D, Dec
         const uint8_t *src = C.ptr(ins.text.s) + ins.t0;
         for (uint32_t i = lane(); i < n_content - D.b_n_content; i += 64) M.content[D.b_n_content + i] = src[i];
     }
-    wave_fence();   // the agent runs and the version map, read lane-parallel from here on
+    fence_workgroup();   // the agent runs and the version map, read lane-parallel from here on
     dirty = false;
 
     // ---- OpParents (decode_oplog.rs:95-148, 856-913) -----------------------------------------
@@ -3256,7 +3190,7 @@ __device__ __forceinline__ int add_doc(const AddParams &P, const AddDesc &D, Dec
             if (crc32c_par(C.in, len - reader_len, L.crc, P.x2n) != want) return ChecksumFailed;
         }
     }
-    wave_fence();
+    fence_workgroup();
 
     // ---- HostOpLog::finish: the new op runs (and the resident's last) split at entry ends ------
     {
@@ -3339,7 +3273,7 @@ __device__ __forceinline__ void add_copy_base(const AddParams &P, const AddDesc 
     const uint2 *bg = reinterpret_cast<const uint2 *>(P.b_agents) + D.b_agent;
     for (uint32_t i = lane(); i < D.b_n_agents; i += 64) M.agents[i] = bg[i];
     if (lane() < D.b_n_ver) M.ver[lane()] = P.b_ver[D.b_ver + lane()];
-    wave_fence();
+    fence_workgroup();
 }
 
 #ifndef DTGPU_ADD_WAVES

@@ -26,30 +26,11 @@
 
 #include "dt_encoder.hpp"
 #include "dt_device.hpp"
+#include "dt_wave.hpp"
 
 namespace dtgpu {
 namespace enc {
-
-#define DEV __device__ __forceinline__
-
-DEV uint32_t lane() { return __lane_id(); }
-DEV uint32_t rdl(uint32_t v, uint32_t l) { return uint32_t(__builtin_amdgcn_readlane(int(v), int(l))); }
-DEV uint64_t ballot(bool p) { return __ballot(p); }
-DEV uint64_t lt_mask() { return (1ull << lane()) - 1ull; }
-DEV uint32_t popc(uint64_t m) { return uint32_t(__popcll(m)); }
-DEV uint32_t ctz(uint64_t m) { return uint32_t(__ffsll((unsigned long long)m) - 1); }
-DEV void wave_fence() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); }
-// inclusive prefix sum over the wave (all lanes active): DPP row scans, then row_bcast 15 / 31
-DEV uint32_t scan_incl(uint32_t v) {
-    v += uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x111, 0xf, 0xf, false));   // row_shr:1
-    v += uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x112, 0xf, 0xf, false));   // row_shr:2
-    v += uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x114, 0xf, 0xf, false));   // row_shr:4
-    v += uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x118, 0xf, 0xf, false));   // row_shr:8
-    v += uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x142, 0xa, 0xf, false));   // row_bcast:15
-    v += uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x143, 0xc, 0xf, false));   // row_bcast:31
-    return v;
-}
-DEV uint32_t wave_sum(uint32_t v) { return uint32_t(__builtin_amdgcn_readlane(int(scan_incl(v)), 63)); }
+using namespace wave;
 
 // wave-wide byte copy, eight loads in flight per lane before their stores
 DEV void copy_bytes(uint8_t *dst, const uint8_t *src, uint32_t n) {
@@ -77,9 +58,7 @@ DEV uint32_t put_leb(uint8_t *d, uint64_t v) {
     return n;
 }
 DEV uint64_t zz_old(int64_t v) { return (uint64_t(v < 0 ? -v : v) << 1) | (v < 0 ? 1u : 0u); }
-DEV uint32_t utf8_len(uint8_t c) { return c < 0x80 ? 1 : (c & 0xE0) == 0xC0 ? 2 : (c & 0xF0) == 0xE0 ? 3 : 4; }
 
-constexpr uint32_t CRC_POLY = 0x82F63B78u;
 constexpr uint32_t ST_OK = 0, ST_CHECKOUT = 64, ST_CAPACITY = 65;
 constexpr uint32_t C_LZ4 = 5, C_FILEINFO = 1, C_DOCID = 2, C_AGENTNAMES = 3, C_STARTBRANCH = 10, C_CONTENT = 13,
                    C_CONTENTCOMP = 14, C_PATCHES = 20, C_OPVERSIONS = 21, C_OPTYPEPOS = 22, C_OPPARENTS = 23,
@@ -102,29 +81,7 @@ DEV uint32_t arun_of(const uint4 *ar, uint32_t n, uint32_t lv) {   // last run w
     return lo ? lo - 1 : 0;
 }
 
-// ---- CRC-32C (zlib's crc32_combine scheme over the reflected polynomial) ------------------------
-DEV uint32_t multmodp(uint32_t a, uint32_t b) {
-    if (!a) return 0;
-    uint32_t m = 1u << 31, p = 0;
-    for (;;) {
-        if (a & m) {
-            p ^= b;
-            if ((a & (m - 1)) == 0) break;
-        }
-        m >>= 1;
-        b = (b & 1u) ? (b >> 1) ^ CRC_POLY : b >> 1;
-    }
-    return p;
-}
-DEV uint32_t x2nmodp(const uint32_t *x2n, uint64_t n, uint32_t k) {
-    uint32_t p = 1u << 31;
-    while (n) {
-        if (n & 1) p = multmodp(x2n[k & 31], p);
-        n >>= 1;
-        k++;
-    }
-    return p;
-}
+// ---- CRC-32C (combine helpers: dt_wave.hpp) ------------------------------------------------------
 // s must be 16-byte aligned: each lane's segment is a multiple of 16 bytes, read as uint4 words
 // with the next word in flight while the current one goes through the table
 DEV uint32_t crc_word(uint32_t c, uint32_t w, const uint32_t *T) {
@@ -498,7 +455,7 @@ __global__ __launch_bounds__(64) void encode_records_kernel(EncParams P) {
         if (l == 0) { R.status = ST_CHECKOUT; P.results[doc] = R; }
         return;
     }
-    wave_fence();
+    fence_workgroup();
     mark(0);
 
     // ---- B: records ------------------------------------------------------------------------------
@@ -618,7 +575,7 @@ __global__ __launch_bounds__(64) void encode_records_kernel(EncParams P) {
                 pb[3 * at] = r.z; pb[3 * at + 1] = r.w + (x - r.x); pb[3 * at + 2] = y - x;
             }
         }
-        wave_fence();
+        fence_workgroup();
         for (uint32_t j0 = 0; j0 < np; j0 += 64) {
             const uint32_t j = j0 + l;
             const bool valid = j < np;
@@ -807,7 +764,7 @@ __global__ __launch_bounds__(64) void encode_records_kernel(EncParams P) {
     }
     if (oy) close_open();
     n_ins = wave_sum(n_ins);
-    wave_fence();
+    fence_workgroup();
     mark(1);
 
     // ---- C: sizes ----------------------------------------------------------------------------------
@@ -930,7 +887,7 @@ __global__ __launch_bounds__(64) void encode_write_kernel(EncParams P) {
     const bool use_lz = compress && text_len >= 20;
     uint32_t lz_len = 0;
     if (use_lz) {
-        wave_fence();
+        fence_workgroup();
         Lz z;
         z.prof = P.prof;
         z.out = lzb;
@@ -952,7 +909,7 @@ __global__ __launch_bounds__(64) void encode_write_kernel(EncParams P) {
             for (int k = 0; k < 3; k++) R.lzst[k] = z.st[k];
         }
     }
-    wave_fence();
+    fence_workgroup();
     R.lz_len = lz_len;
     mark(3);
 
@@ -1140,7 +1097,7 @@ __global__ __launch_bounds__(64) void encode_write_kernel(EncParams P) {
             base += rdl(incl, 63);
         }
     }
-    wave_fence();
+    fence_workgroup();
     mark(4);
 
     // ---- G: CRC chunk --------------------------------------------------------------------------------

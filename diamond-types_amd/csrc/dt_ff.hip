@@ -21,42 +21,18 @@
 
 #include "dt_ff.hpp"
 #include "dt_host.hpp"
+#include "dt_wave.hpp"
 
 namespace dtgpu {
 namespace ff {
-
-typedef unsigned long long u64;
-#define DEV __device__ __forceinline__
-
-DEV uint32_t lane_id() { return __lane_id(); }
-DEV void wave_fence() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier(); }
-DEV uint32_t bcast(uint32_t v, uint32_t l) { return uint32_t(__builtin_amdgcn_readlane(int(v), int(l))); }
-DEV uint32_t first_lane(u64 m) { return uint32_t(__ffsll((long long)m) - 1); }
-// inclusive 64-lane prefix sum (DPP row shifts, then row_bcast 15 / 31), as dt_replay.hip
-DEV uint32_t wave_scan(uint32_t x) {
-    x += uint32_t(__builtin_amdgcn_update_dpp(0, int(x), 0x111, 0xF, 0xF, false));
-    x += uint32_t(__builtin_amdgcn_update_dpp(0, int(x), 0x112, 0xF, 0xF, false));
-    x += uint32_t(__builtin_amdgcn_update_dpp(0, int(x), 0x114, 0xF, 0xF, false));
-    x += uint32_t(__builtin_amdgcn_update_dpp(0, int(x), 0x118, 0xF, 0xF, false));
-    x += uint32_t(__builtin_amdgcn_update_dpp(0, int(x), 0x142, 0xA, 0xF, false));
-    x += uint32_t(__builtin_amdgcn_update_dpp(0, int(x), 0x143, 0xC, 0xF, false));
-    return x;
-}
-DEV uint32_t wave_sum(uint32_t v) { return bcast(wave_scan(v), 63); }
-DEV u64 splitmix(u64 z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-DEV uint32_t utf8_len(uint8_t c) { return c < 0x80 ? 1 : (c & 0xE0) == 0xC0 ? 2 : (c & 0xF0) == 0xE0 ? 3 : 4; }
+using namespace wave;
 
 // Exclusive prefix sum over a workgroup of NT threads (wave scans + one LDS round for the wave
 // totals); *total = the sum.  s_w holds NT / 64 + 1 words.  Ends with a barrier.
 template <uint32_t NT>
 DEV uint32_t block_scan(uint32_t x, uint32_t *s_w, uint32_t &total) {
-    const uint32_t l = lane_id(), w = threadIdx.x / 64;
-    const uint32_t inc = wave_scan(x);
+    const uint32_t l = lane(), w = threadIdx.x / 64;
+    const uint32_t inc = scan_incl(x);
     if (l == 63) s_w[w] = inc;
     __syncthreads();
     uint32_t base = 0, tot = 0;
@@ -91,7 +67,7 @@ __global__ __launch_bounds__(256) void ff_delta_kernel(FFParams P) {
 __global__ __launch_bounds__(64) void ff_seg_kernel(FFParams P) {
     __shared__ uint4 sv[FF_PIECES / 2 + 1];   // re-pack area: piece j at uint2 slot j
     uint2 *sp = reinterpret_cast<uint2 *>(sv);
-    const uint32_t l = lane_id();
+    const uint32_t l = lane();
     const uint32_t gs = blockIdx.x;
     const FFSeg g = P.segs[gs];
     const FFDoc &D = P.docs[g.doc];
@@ -111,27 +87,27 @@ __global__ __launch_bounds__(64) void ff_seg_kernel(FFParams P) {
     uint32_t bad = int32_t(lin) < 0 ? 1u : 0u;   // more deleted than inserted before this segment
     const uint32_t j0 = 2 * l, j1 = 2 * l + 1;
     for (uint32_t r = 0; r < g.nrun && !bad; r++) {
-        const uint32_t lv = bcast(run.x, r), len = bcast(run.y, r), pos = bcast(run.z, r);
-        const bool del = (bcast(run.w, r) & 1u) != 0;
+        const uint32_t lv = rdl(run.x, r), len = rdl(run.y, r), pos = rdl(run.z, r);
+        const bool del = (rdl(run.w, r) & 1u) != 0;
         const uint32_t pair = l0 + l1;
-        const uint32_t inc = wave_scan(pair);
-        const uint32_t total = bcast(inc, 63);
+        const uint32_t inc = scan_incl(pair);
+        const uint32_t total = rdl(inc, 63);
         const uint32_t e0 = inc - pair, e1 = e0 + l0;
         if (!del) {
             if (pos > total || len == 0) { bad = 1; break; }
             // the piece holding pos (none: pos is the end of the text)
             const bool c0 = pos - e0 < l0, c1 = pos - e1 < l1;   // (unsigned: e <= pos < e + len)
-            const u64 m = __ballot(c0 || c1);
+            const u64 m = ballot(c0 || c1);
             uint32_t k = n, off = 0;
             if (m) {
-                const uint32_t kl = first_lane(m);
-                const uint32_t in0 = bcast(c0 ? 1u : 0u, kl);
+                const uint32_t kl = ctz(m);
+                const uint32_t in0 = rdl(c0 ? 1u : 0u, kl);
                 k = 2 * kl + (in0 ? 0u : 1u);
-                off = pos - bcast(in0 ? e0 : e1, kl);
+                off = pos - rdl(in0 ? e0 : e1, kl);
             }
             if (off == 0 && k > 0) {   // the run continues the piece before it (typing)
                 const uint32_t pl = (k - 1) >> 1, ph = (k - 1) & 1u;
-                const uint32_t ps = bcast(ph ? s1 : s0, pl), pn = bcast(ph ? l1 : l0, pl);
+                const uint32_t ps = rdl(ph ? s1 : s0, pl), pn = rdl(ph ? l1 : l0, pl);
                 if (!(ps & FF_PH) && ps + pn == lv) {
                     if (l == pl) { if (ph) l1 += len; else l0 += len; }
                     continue;
@@ -159,23 +135,23 @@ __global__ __launch_bounds__(64) void ff_seg_kernel(FFParams P) {
             const uint32_t L0 = a0 < pos ? min(b0, pos) - a0 : 0u, R0 = b0 > de ? b0 - max(a0, de) : 0u;
             const uint32_t L1 = a1 < pos ? min(b1, pos) - a1 : 0u, R1 = b1 > de ? b1 - max(a1, de) : 0u;
             const uint32_t c = (L0 ? 1u : 0u) + (R0 ? 1u : 0u) + (L1 ? 1u : 0u) + (R1 ? 1u : 0u);
-            const uint32_t ci = wave_scan(c);
+            const uint32_t ci = scan_incl(c);
             uint32_t o = ci - c;
             if (L0) sp[o++] = make_uint2(s0, L0);
             if (R0) sp[o++] = make_uint2(s0 + (max(a0, de) - a0), R0);
             if (L1) sp[o++] = make_uint2(s1, L1);
             if (R1) sp[o++] = make_uint2(s1 + (max(a1, de) - a1), R1);
-            n = bcast(ci, 63);
+            n = rdl(ci, 63);
         }
-        wave_fence();
+        fence_wave();
         const uint4 v = sv[l];
         s0 = j0 < n ? v.x : 0u; l0 = j0 < n ? v.y : 0u;
         s1 = j1 < n ? v.z : 0u; l1 = j1 < n ? v.w : 0u;
-        wave_fence();
+        fence_wave();
     }
     if (bad && l == 0) P.bad[g.doc] = 1;
     const uint32_t pair = l0 + l1;
-    const uint32_t e0 = wave_scan(pair) - pair;
+    const uint32_t e0 = scan_incl(pair) - pair;
     uint4 *out = reinterpret_cast<uint4 *>(P.pa) + D.piece_off + size_t(FF_PIECES) * li;
     if (j0 < n) out[j0] = make_uint4(s0, l0, e0, 0);
     if (j1 < n) out[j1] = make_uint4(s1, l1, e0 + l0, 0);
@@ -379,7 +355,7 @@ __global__ __launch_bounds__(XT) void ff_copy_kernel(FFParams P) {
     }
 #pragma unroll
     for (int k = 32; k >= 1; k >>= 1) h += __shfl_xor(h, k, 64);
-    if (lane_id() == 0) s_h[t / 64] = h;
+    if (lane() == 0) s_h[t / 64] = h;
     __syncthreads();
     if (t == 0) {
         u64 sum = 0;

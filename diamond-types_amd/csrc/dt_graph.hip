@@ -22,9 +22,11 @@
 
 #include "dt_graph.hpp"
 #include "dt_device.hpp"
+#include "dt_wave.hpp"
 
 namespace dtgpu {
 namespace gdev {
+using namespace wave;
 
 constexpr int KEY_CAP = 256;     // diff / contains queue in LDS (entries)
 constexpr int TP_CAP = 64;       // find_conflicting queue in LDS (time points)
@@ -100,7 +102,7 @@ struct Spans {
     __device__ __forceinline__ void flush() {
         if (!have) return;
         if (n >= cap) { overflow = true; have = false; return; }
-        if (__lane_id() == 0) {
+        if (lane() == 0) {
             out[words * n] = uint32_t(ls);
             out[words * n + 1] = uint32_t(le);
             if (words == 3) out[words * n + 2] = lf;
@@ -122,7 +124,7 @@ struct Common {
     bool overflow;
     __device__ __forceinline__ void push(int32_t v) {
         if (n >= cap) { overflow = true; return; }
-        if (__lane_id() == 0) out[n] = v;
+        if (lane() == 0) out[n] = v;
         n++;
     }
 };
@@ -272,7 +274,7 @@ __device__ __forceinline__ uint32_t q_dominators(const G &g, const GraphQuery &q
     }
     if (out.overflow) return GQ_OVERFLOW;
     // ascending: reverse the slot in place (lane 0 wrote it)
-    if (__lane_id() == 0) {
+    if (lane() == 0) {
         for (uint32_t i = 0, n = out.n; i < n / 2; i++) {
             const int32_t x = out.out[i], y = out.out[n - 1 - i];
             out.out[i] = y;
@@ -485,7 +487,7 @@ __global__ __launch_bounds__(64) void graph_query_kernel(GraphParams P) {
     }
     if (BIG && st == GQ_QUEUE_FULL) st = GQ_OVERFLOW;   // cannot happen: the scratch is sized from the graph
     r.status = st;
-    if (__lane_id() == 0) P.results[qi] = r;
+    if (lane() == 0) P.results[qi] = r;
 }
 
 }  // namespace gdev

@@ -23,45 +23,17 @@
 
 #include "dt_device.hpp"
 #include "dt_history.hpp"
+#include "dt_wave.hpp"
 
 namespace dtgpu {
 namespace hist {
+using namespace wave;
 
 enum : uint32_t { S_OK = 0, ErrCapacity = 65, ErrArg = 67, Defer = DECODE_DEFER };
 constexpr uint32_t NONE = 0xFFFFFFFFu;
 
-__device__ __forceinline__ uint32_t lane() { return __lane_id(); }
-__device__ __forceinline__ uint32_t rdl(uint32_t v, uint32_t l) {
-    return uint32_t(__builtin_amdgcn_readlane(int(v), int(l)));
-}
-__device__ __forceinline__ uint64_t ballot(bool p) { return __ballot(p); }
-__device__ __forceinline__ uint64_t lt_mask() { return (1ull << lane()) - 1ull; }
-__device__ __forceinline__ uint32_t popc(uint64_t m) { return uint32_t(__popcll(m)); }
-// inclusive prefix sum / prefix maximum over the wave (all lanes active; dt_decode.hip scan_incl)
-__device__ __forceinline__ uint32_t scan_incl(uint32_t v) {
-    v += uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x111, 0xf, 0xf, false));   // row_shr:1
-    v += uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x112, 0xf, 0xf, false));   // row_shr:2
-    v += uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x114, 0xf, 0xf, false));   // row_shr:4
-    v += uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x118, 0xf, 0xf, false));   // row_shr:8
-    v += uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x142, 0xa, 0xf, false));   // row_bcast:15
-    v += uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x143, 0xc, 0xf, false));   // row_bcast:31
-    return v;
-}
 __device__ __forceinline__ uint32_t umax(uint32_t a, uint32_t b) { return a > b ? a : b; }
 __device__ __forceinline__ uint32_t umin(uint32_t a, uint32_t b) { return a < b ? a : b; }
-__device__ __forceinline__ uint32_t scan_max(uint32_t v) {
-    v = umax(v, uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x111, 0xf, 0xf, false)));
-    v = umax(v, uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x112, 0xf, 0xf, false)));
-    v = umax(v, uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x114, 0xf, 0xf, false)));
-    v = umax(v, uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x118, 0xf, 0xf, false)));
-    v = umax(v, uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x142, 0xa, 0xf, false)));
-    v = umax(v, uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x143, 0xc, 0xf, false)));
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) { return rdl(scan_incl(v), 63); }
-// this wave's stores and atomics have reached L2 and its later loads see them
-__device__ __forceinline__ void mem_fence() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent"); }
-__device__ __forceinline__ uint32_t utf8_len(uint8_t c) { return c < 0x80 ? 1 : (c & 0xE0) == 0xC0 ? 2 : (c & 0xF0) == 0xE0 ? 3 : 4; }
 
 // The last index i < n with a[i * stride] <= key (a ascending, a[0] <= key, n >= 1).
 __device__ __forceinline__ uint32_t find_le(const uint32_t *a, uint32_t stride, uint32_t n, uint32_t key) {
@@ -135,7 +107,7 @@ __device__ __forceinline__ uint32_t mark_doc(const HistParams &P, const HistDesc
     if (D.b_n_lv >= 0x7FFFFFFEu) return Defer;   // (x + 1) << 1 must fit the mark word
     uint32_t *W = D.use_lds ? lds : S.reach;
     for (uint32_t i = L; i < ne; i += 64) W[i] = 0;
-    mem_fence();
+    fence_agent();
     {   // seed
         const uint32_t *req = P.req + D.req_off;
         bool bad = false;
@@ -152,7 +124,7 @@ __device__ __forceinline__ uint32_t mark_doc(const HistParams &P, const HistDesc
         const uint32_t e = valid ? uint32_t(es) : 0;
         bool pushed = false;
         for (;;) {
-            mem_fence();
+            fence_agent();
             const uint32_t w = valid ? __hip_atomic_load(&W[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
             const bool go = valid && w != 0 && !pushed;
             if (!ballot(go)) break;
@@ -166,7 +138,7 @@ __device__ __forceinline__ uint32_t mark_doc(const HistParams &P, const HistDesc
             }
         }
     }
-    mem_fence();
+    fence_agent();
     // prefix ends, the LV map, the reduced frontier, bounds of entries / parents / agent runs
     uint32_t total = 0, nfront = 0, n_ent = 0, n_par = 0, n_ar = 0;
     uint32_t *front = P.o_front + D.o_ver, *ver = P.o_ver + D.o_ver;
@@ -190,7 +162,7 @@ __device__ __forceinline__ uint32_t mark_doc(const HistParams &P, const HistDesc
         n_ar += wave_sum(inc ? find_le(B.aruns, 4, D.b_n_aruns, r - 1) - find_le(B.aruns, 4, D.b_n_aruns, st) + 1 : 0);
     }
     if (nfront > DECODE_MAX_FRONTIER) return Defer;
-    mem_fence();
+    fence_agent();
     // op runs that intersect the history, their content bytes
     uint32_t n_op = 0, n_bytes = 0;
     for (uint32_t i0 = 0; i0 < D.b_n_ops; i0 += 64) {
@@ -525,11 +497,11 @@ __device__ __forceinline__ uint32_t emit_doc(const HistParams &P, const HistDesc
     if (!emit_entries(D, B, S, O, n_lv, n_ent, n_par)) return ErrCapacity;
     const uint32_t apieces = arun_pieces(D, B, S, O);
     if (apieces == NONE) return ErrCapacity;
-    mem_fence();   // the pieces and the entry heads, before the passes that read them
+    fence_agent();   // the pieces and the entry heads, before the passes that read them
     const uint32_t n_aruns = merge_pass<false>(O.aruns, apieces);
     OpTotals T;
     if (!op_pieces(D, B, S, O, T)) return ErrCapacity;
-    mem_fence();
+    fence_agent();
     const uint32_t n_ops = merge_pass<true>(O.ops, T.n_pieces);
     if (T.n_bytes > D.c_content) return ErrCapacity;
     if (!fill_lvs(D, B, S, O, n_lv)) return ErrCapacity;

@@ -39,9 +39,11 @@
 
 #include "dt_graph.hpp"
 #include "dt_device.hpp"
+#include "dt_wave.hpp"
 
 namespace dtgpu {
 namespace ldev {
+using namespace wave;
 
 struct Ent { int32_t start, end, shadow; uint32_t poff; };
 
@@ -331,7 +333,6 @@ struct Sweep {
     }
 };
 
-__device__ __forceinline__ uint32_t rdlane(uint32_t v, uint32_t l) { return uint32_t(__builtin_amdgcn_readlane(int(v), int(l))); }
 
 // LM: marks and bucket heads in LDS.  LP (first pass): the time points and sorted buckets in LDS;
 // a query that outgrows them ends at GQ_QUEUE_FULL and is answered again by the !LP launch, which
@@ -468,10 +469,10 @@ __global__ __launch_bounds__(256) void level_conflict_kernel(LevelParams P, Grap
                 bj = 0;
             }
             const int32_t hv = lane >= bj && lane < bhave ? head[b_e] : -1;
-            const uint64_t m = __ballot(hv >= 0);
+            const uint64_t m = ballot(hv >= 0);
             if (m) {
-                jj = uint32_t(__ffsll((long long)m) - 1);
-                e = int32_t(rdlane(b_e, jj));
+                jj = ctz(m);
+                e = int32_t(rdl(b_e, jj));
                 bj = jj + 1;
                 break;
             }
@@ -510,7 +511,7 @@ __global__ __launch_bounds__(256) void level_conflict_kernel(LevelParams P, Grap
             break;
         }
         for (uint32_t k = 0; k + 1 < S.size(T); k++) S.push_elem(T, k, flag);   // shatter
-        const int32_t es = int32_t(rdlane(uint32_t(b_s), jj));
+        const int32_t es = int32_t(rdl(uint32_t(b_s), jj));
         int32_t re = S.last(T) + 1;
         bool stopped = false;
         for (; i < m; i++) {   // the other points inside this entry, highest first
@@ -533,7 +534,7 @@ __global__ __launch_bounds__(256) void level_conflict_kernel(LevelParams P, Grap
         if (stopped) break;
         sp.push(es, re, mflag(uint32_t(e), re - 1));
         for (uint32_t k = 0; k < m; k++) S.release(bk[k]);   // every point of the bucket is consumed
-        S.push(TP_PARENTS, uint32_t(e), rdlane(b_np, jj), flag, int32_t(rdlane(uint32_t(b_lp), jj)), rdlane(b_lpe, jj));
+        S.push(TP_PARENTS, uint32_t(e), rdl(b_np, jj), flag, int32_t(rdl(uint32_t(b_lp), jj)), rdl(b_lpe, jj));
     }
     if (st == GQ_OK && S.overflow) st = LP ? GQ_QUEUE_FULL : GQ_OVERFLOW;
     sp.flush();

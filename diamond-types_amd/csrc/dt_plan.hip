@@ -26,27 +26,11 @@
 #include <stdint.h>
 
 #include "dt_device.hpp"
+#include "dt_wave.hpp"
 
 namespace dtgpu {
 namespace pdev {
-
-typedef unsigned long long u64;
-#define DEV __device__ __forceinline__
-
-DEV uint32_t lane_id() { return __lane_id(); }
-DEV uint32_t U(uint32_t v) { return uint32_t(__builtin_amdgcn_readfirstlane(int(v))); }
-DEV uint32_t bcast(uint32_t v, uint32_t l) { return uint32_t(__builtin_amdgcn_readlane(int(v), int(l))); }
-DEV uint32_t first_lane(u64 m) { return uint32_t(__ffsll((long long)m) - 1); }
-DEV void wave_fence() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier(); }
-DEV uint32_t wave_scan(uint32_t x) {   // inclusive prefix sum (same DPP sequence as dt_replay.hip)
-    x += uint32_t(__builtin_amdgcn_update_dpp(0, int(x), 0x111, 0xF, 0xF, false));
-    x += uint32_t(__builtin_amdgcn_update_dpp(0, int(x), 0x112, 0xF, 0xF, false));
-    x += uint32_t(__builtin_amdgcn_update_dpp(0, int(x), 0x114, 0xF, 0xF, false));
-    x += uint32_t(__builtin_amdgcn_update_dpp(0, int(x), 0x118, 0xF, 0xF, false));
-    x += uint32_t(__builtin_amdgcn_update_dpp(0, int(x), 0x142, 0xA, 0xF, false));
-    x += uint32_t(__builtin_amdgcn_update_dpp(0, int(x), 0x143, 0xC, 0xF, false));
-    return x;
-}
+using namespace wave;
 
 struct P {
     // inputs (decoded oplog)
@@ -75,10 +59,10 @@ struct P {
 // DTGPU_PLAN_PROF cycle counters: in LDS, so that the (usually off) profile holds no SGPRs
 __shared__ uint64_t g_pc[7];   // six phases, then the last timestamp
 DEV void tk(const P &p) {
-    if (p.prof && lane_id() == 0) { for (int i = 0; i < 6; i++) g_pc[i] = 0; g_pc[6] = __builtin_amdgcn_s_memtime(); }
+    if (p.prof && lane() == 0) { for (int i = 0; i < 6; i++) g_pc[i] = 0; g_pc[6] = __builtin_amdgcn_s_memtime(); }
 }
 #define PT(slot) do { if (p.prof) { const uint64_t t_ = __builtin_amdgcn_s_memtime(); \
-    if (lane_id() == 0) { g_pc[slot] += t_ - g_pc[6]; g_pc[6] = t_; } } } while (0)
+    if (lane() == 0) { g_pc[slot] += t_ - g_pc[6]; g_pc[6] = t_; } } } while (0)
 
 DEV void fail(P &p, uint32_t code) {
     if (!p.err) p.err = code;
@@ -94,10 +78,10 @@ enum {
     R_PENT0, R_PCH0, R_PCNT0, R_PENT1, R_PCH1, R_PCNT1, R_LASTCH, R_FIRSTCH
 };
 DEV uint32_t load_rec(const P &p, uint32_t e) {
-    const uint32_t l = lane_id();
+    const uint32_t l = lane();
     return l < EREC_WORDS ? p.erec[erec_word(p.ne, e, l)] : 0;
 }
-DEV uint32_t R(uint32_t rw, int k) { return U(bcast(rw, uint32_t(k))); }
+DEV uint32_t R(uint32_t rw, int k) { return U(rdl(rw, uint32_t(k))); }
 
 template <int K> struct VV { uint32_t v[K]; };
 
@@ -116,7 +100,7 @@ template <int K> DEV bool vv_differ(const VV<K> &x, const VV<K> &y) {
     return __ballot(d) != 0;
 }
 template <int K> DEV void load_row(const P &p, uint32_t e, VV<K> &row) {
-    const uint32_t l = lane_id();
+    const uint32_t l = lane();
 #pragma unroll
     for (int k = 0; k < K; k++) {
         const uint32_t a = l + 64 * k;
@@ -124,7 +108,7 @@ template <int K> DEV void load_row(const P &p, uint32_t e, VV<K> &row) {
     }
 }
 template <int K> DEV void store_row(P &p, uint32_t e, const VV<K> &row) {
-    const uint32_t l = lane_id();
+    const uint32_t l = lane();
 #pragma unroll
     for (int k = 0; k < K; k++) {
         const uint32_t a = l + 64 * k;
@@ -138,7 +122,7 @@ template <int K> DEV void store_row(P &p, uint32_t e, const VV<K> &row) {
 template <int K>
 DEV void fold_entry(P &p, uint32_t start, uint32_t end, uint32_t upto, uint32_t c, uint32_t s0, VV<K> &row,
                     bool check) {
-    const uint32_t l = lane_id();
+    const uint32_t l = lane();
     const uint32_t hi = min(end, upto + 1);
     if (c >= p.A || hi <= start) { fail(p, PLAN_ERR_INTERNAL); return; }
     bool bad = false;
@@ -165,7 +149,7 @@ template <int K> DEV void vv_at(P &p, uint32_t lv, uint32_t e, VV<K> &row) {
 // gathered together, 64 entries per load.
 template <int K>
 DEV void emit_diff(P &p, const VV<K> &from, const VV<K> &to, const VV<K> &dlo, const VV<K> &dhi, bool allow_retreat) {
-    const uint32_t l = lane_id();
+    const uint32_t l = lane();
 #pragma unroll
     for (int k = 0; k < K; k++) {
         const uint32_t a = l + 64 * k;
@@ -178,9 +162,9 @@ DEV void emit_diff(P &p, const VV<K> &from, const VV<K> &to, const VV<K> &dlo, c
         const uint32_t n = act ? (adv ? to.v[k] - from.v[k] : from.v[k] - to.v[k]) : 0;
         const uint32_t d0 = dlo.v[k], d1 = dhi.v[k];
         if (__ballot(act && d0 + s0 + n > d1)) { fail(p, PLAN_ERR_INTERNAL); return; }
-        const uint32_t inc = wave_scan(n);
-        const uint32_t total = bcast(inc, 63);
-        const uint32_t n_adv = bcast(wave_scan(adv ? n : 0), 63);
+        const uint32_t inc = scan_incl(n);
+        const uint32_t total = rdl(inc, 63);
+        const uint32_t n_adv = rdl(scan_incl(adv ? n : 0), 63);
         if (uint64_t(p.nt) + total > p.tcap) { fail(p, PLAN_TLIST_FULL); return; }
         if (!p.count_only) {
             const uint32_t src = d0 + s0, off = inc - n;   // per agent lane
@@ -189,9 +173,9 @@ DEV void emit_diff(P &p, const VV<K> &from, const VV<K> &to, const VV<K> &dlo, c
                 const uint32_t u = c + l;
                 uint32_t from_idx = 0, flag = 0;
                 for (u64 m = am; m; m &= m - 1) {   // the agent whose output slice holds u
-                    const uint32_t j = first_lane(m);
-                    const uint32_t o = U(bcast(off, j)), nn = U(bcast(n, j));
-                    const uint32_t sj = U(bcast(src, j)), fj = U(bcast(adv ? TL_ADV : 0u, j));
+                    const uint32_t j = ctz(m);
+                    const uint32_t o = U(rdl(off, j)), nn = U(rdl(n, j));
+                    const uint32_t sj = U(rdl(src, j)), fj = U(rdl(adv ? TL_ADV : 0u, j));
                     if (u >= o && u < o + nn) { from_idx = sj + (u - o); flag = fj; }
                 }
                 if (u < total) {
@@ -221,7 +205,7 @@ struct Emit {
 };
 DEV void emit_issue(P &p, const VV<1> &from, const VV<1> &to, const VV<1> &dlo, const VV<1> &dhi,
                     bool allow_retreat, Emit &E) {
-    const uint32_t l = lane_id();
+    const uint32_t l = lane();
     const bool act = l < p.A && from.v[0] != to.v[0];
     E.am = __ballot(act);
     E.any = E.am != 0;
@@ -233,22 +217,22 @@ DEV void emit_issue(P &p, const VV<1> &from, const VV<1> &to, const VV<1> &dlo, 
     const uint32_t s0 = adv ? from.v[0] : to.v[0];
     const uint32_t n = act ? (adv ? to.v[0] - from.v[0] : from.v[0] - to.v[0]) : 0;
     if (__ballot(act && dlo.v[0] + s0 + n > dhi.v[0])) { fail(p, PLAN_ERR_INTERNAL); E.any = false; return; }
-    const uint32_t inc = wave_scan(n);
-    E.total = bcast(inc, 63);
-    E.n_adv = bcast(wave_scan(adv ? n : 0), 63);
+    const uint32_t inc = scan_incl(n);
+    E.total = rdl(inc, 63);
+    E.n_adv = rdl(scan_incl(adv ? n : 0), 63);
     E.off = inc - n; E.n = n; E.src = dlo.v[0] + s0; E.fl = adv ? TL_ADV : 0u;
     if (p.count_only) return;
     uint32_t from_idx = 0, flag = 0;
     for (u64 m = E.am; m; m &= m - 1) {   // the chain whose output slice holds lane l (few chains move)
-        const uint32_t j = first_lane(m);
-        const uint32_t o = U(bcast(E.off, j)), nn = U(bcast(E.n, j));
+        const uint32_t j = ctz(m);
+        const uint32_t o = U(rdl(E.off, j)), nn = U(rdl(E.n, j));
         if (o >= 64) break;
-        if (l >= o && l < o + nn) { from_idx = U(bcast(E.src, j)) + (l - o); flag = U(bcast(E.fl, j)); }
+        if (l >= o && l < o + nn) { from_idx = U(rdl(E.src, j)) + (l - o); flag = U(rdl(E.fl, j)); }
     }
     if (l < E.total) { E.dv = p.dense[from_idx]; E.dfl = flag; }
 }
 DEV void emit_store(P &p, const Emit &E) {
-    const uint32_t l = lane_id();
+    const uint32_t l = lane();
     if (uint64_t(p.nt) + E.total > p.tcap) { fail(p, PLAN_TLIST_FULL); return; }
     if (!p.count_only) {
         bool bad = l < E.total && E.dv == 0xFFFFFFFFu;
@@ -257,9 +241,9 @@ DEV void emit_store(P &p, const Emit &E) {
         // dense table
         if (E.total > 64) {
             for (u64 m = E.am; m; m &= m - 1) {
-                const uint32_t j = first_lane(m);
-                const uint32_t o = U(bcast(E.off, j)), nn = U(bcast(E.n, j));
-                const uint32_t src = U(bcast(E.src, j)), fl = U(bcast(E.fl, j));
+                const uint32_t j = ctz(m);
+                const uint32_t o = U(rdl(E.off, j)), nn = U(rdl(E.n, j));
+                const uint32_t src = U(rdl(E.src, j)), fl = U(rdl(E.fl, j));
                 const uint32_t a = max(o, 64u), b = o + nn;
                 for (uint32_t u0 = a; u0 < b; u0 += 64) {
                     const uint32_t u = u0 + l;
@@ -280,7 +264,7 @@ DEV void emit_store(P &p, const Emit &E) {
 
 DEV void push_cmd(P &p, uint32_t op, uint32_t a, uint32_t n, uint32_t pos) {
     if (uint64_t(p.nc) >= p.ccap) { fail(p, PLAN_CMDS_FULL); return; }
-    if (lane_id() == 0 && !p.count_only) p.cmds[p.nc] = Cmd{op, a, n, pos};
+    if (lane() == 0 && !p.count_only) p.cmds[p.nc] = Cmd{op, a, n, pos};
     p.nc++;
 }
 
@@ -289,7 +273,7 @@ constexpr uint8_t MERGE_BIT = 0x80;   // pending byte: parent count (<= 127) | m
 // Next entry to consume: the todo top, unless it is a merge and a non-merge is ready
 // (txn_trace.rs:249-266).  Pops it.
 DEV uint32_t pick(P &p, uint32_t &top) {
-    const uint32_t l = lane_id();
+    const uint32_t l = lane();
     uint32_t idx = U(p.todo[top - 1]);
     if (p.pending[idx] & MERGE_BIT) {
         int found = -1;
@@ -297,12 +281,12 @@ DEV uint32_t pick(P &p, uint32_t &top) {
             const int i = hi - int(l);
             const bool ok = i >= 0 && !(p.pending[p.todo[i]] & MERGE_BIT);
             const u64 m = __ballot(ok);
-            if (m) found = hi - int(first_lane(m));
+            if (m) found = hi - int(ctz(m));
         }
         if (found >= 0) {
             idx = U(p.todo[found]);
             if (l == 0) p.todo[found] = p.todo[top - 1];
-            wave_fence();
+            fence_wave();
         }
     }
     top--;
@@ -311,7 +295,7 @@ DEV uint32_t pick(P &p, uint32_t &top) {
 
 template <int K>
 DEV void plan_doc(P &p, PlanResult *res) {
-    const uint32_t l = lane_id();
+    const uint32_t l = lane();
     VV<K> vf, vp, dlo, dhi;
     vv_zero(vf);
     // each chain's dense-table slice, kept in registers
@@ -343,7 +327,7 @@ DEV void plan_doc(P &p, PlanResult *res) {
         top += uint32_t(__popcll(m));
     }
     if (__ballot(bad_np)) fail(p, PLAN_WIDE_MERGE);
-    wave_fence();
+    fence_wave();
     tk(p);
     PT(5);
     uint32_t f = 0xFFFFFFFFu;   // current frontier: ROOT or one LV
@@ -436,7 +420,7 @@ DEV void plan_doc(P &p, PlanResult *res) {
             if (ready) p.todo[top + rank] = uint16_t(chv);
             top += uint32_t(__popcll(m));
         }
-        wave_fence();
+        fence_wave();
         have = top > 0;
         if (have) {
             idx = pick(p, top);
@@ -517,7 +501,7 @@ DEV void plan_doc(P &p, PlanResult *res) {
 // s_load would wait for it -- measured slower.)
 struct Rec { uint32_t w, row; };   // the record and the entry's parent version vector (lane = chain)
 DEV Rec srec(const P &p, uint32_t e) {
-    const uint32_t l = lane_id();
+    const uint32_t l = lane();
     return Rec{load_rec(p, e), l < p.A ? p.prow[size_t(e) * p.row_stride + l] : 0u};
 }
 DEV uint32_t F(const Rec &r, int k) { return R(r.w, k); }
@@ -534,7 +518,7 @@ struct Stk {
 };
 // Push the lanes of `ready` (child index order = lane order), entry in chv, merge flag in mg.
 DEV bool stk_push(P &p, Stk &S, u64 ready, uint32_t chv, bool mg) {
-    const uint32_t l = lane_id();
+    const uint32_t l = lane();
     const uint32_t cnt = uint32_t(__popcll(ready));
     if (!cnt) return true;
     if (S.nl + S.n + cnt > PLAN_TODO_CAP) { fail(p, PLAN_TODO_FULL); return false; }
@@ -543,14 +527,14 @@ DEV bool stk_push(P &p, Stk &S, u64 ready, uint32_t chv, bool mg) {
         S.nl += S.n;
         S.n = 0;
         S.mm = 0;
-        wave_fence();
+        fence_wave();
     }
     // ready lanes in lane order onto positions n, n + 1, ... (usually one or two)
     const u64 mgm = __ballot(mg);
     uint32_t at = S.n;
     for (u64 r = ready; r; r &= r - 1, at++) {
-        const uint32_t j = first_lane(r);
-        const uint32_t e = bcast(chv, j);
+        const uint32_t j = ctz(r);
+        const uint32_t e = rdl(chv, j);
         S.v = l == at ? e : S.v;
         if ((mgm >> j) & 1ull) S.mm |= 1ull << at;
     }
@@ -559,7 +543,7 @@ DEV bool stk_push(P &p, Stk &S, u64 ready, uint32_t chv, bool mg) {
 }
 // Pop the next entry (as pick()); has_any: S.n + S.nl > 0.
 DEV uint32_t stk_pick(P &p, Stk &S) {
-    const uint32_t l = lane_id();
+    const uint32_t l = lane();
     if (S.n == 0) {   // refill from LDS: its top 32 (or fewer) positions
         const uint32_t k = min(S.nl, 32u);
         const uint32_t base = S.nl - k;
@@ -571,12 +555,12 @@ DEV uint32_t stk_pick(P &p, Stk &S) {
         S.nl = base;
     }
     const uint32_t t = S.n - 1;
-    uint32_t idx = bcast(S.v, t);
+    uint32_t idx = rdl(S.v, t);
     if ((S.mm >> t) & 1ull) {
         const u64 nm = ~S.mm & ((1ull << t) - 1ull);
         if (nm) {   // the highest non-merge below the top takes its place
             const uint32_t pos = 63u - uint32_t(__clzll((long long)nm));
-            const uint32_t x = bcast(S.v, pos);
+            const uint32_t x = rdl(S.v, pos);
             S.v = l == pos ? idx : S.v;
             S.mm |= 1ull << pos;
             idx = x;
@@ -586,12 +570,12 @@ DEV uint32_t stk_pick(P &p, Stk &S) {
                 const int i = hi - int(l);
                 const bool ok = i >= 0 && !(p.pending[p.todo[i]] & MERGE_BIT);
                 const u64 m = __ballot(ok);
-                if (m) found = hi - int(first_lane(m));
+                if (m) found = hi - int(ctz(m));
             }
             if (found >= 0) {
                 const uint32_t x = U(p.todo[found]);
                 if (l == 0) p.todo[found] = uint16_t(idx);
-                wave_fence();
+                fence_wave();
                 idx = x;
             }
         }
@@ -602,7 +586,7 @@ DEV uint32_t stk_pick(P &p, Stk &S) {
 }
 
 DEV void plan_doc1(P &p, PlanResult *res) {
-    const uint32_t l = lane_id();
+    const uint32_t l = lane();
     const uint32_t dlo = l < p.A ? p.doff[l] : 0, dhi = l < p.A ? p.doff[l + 1] : 0;
     VV<1> dl, dh;
     dl.v[0] = dlo; dh.v[0] = dhi;
@@ -627,7 +611,7 @@ DEV void plan_doc1(P &p, PlanResult *res) {
         top += uint32_t(__popcll(m));
     }
     if (__ballot(bad_np)) fail(p, PLAN_WIDE_MERGE);
-    wave_fence();
+    fence_wave();
     Stk S;
     S.v = 0; S.mm = 0; S.n = 0; S.nl = top;
     tk(p);
@@ -769,7 +753,7 @@ constexpr uint32_t kSplitRegChains = 4;   // up to this many moving chains per s
 constexpr uint32_t kSplitSegChunk = 4096;
 constexpr uint32_t kSplitCopyDepth = 8;   // big steps: 8 x 64 dense-table loads per round trip   // ... for chunks writing up to this many entries / commands
 DEV void plan_doc_split(P &p, PlanResult *res) {
-    const uint32_t l = lane_id();
+    const uint32_t l = lane();
     uint32_t top = 0;
     bool bad_np = false;
     for (uint32_t c = 0; c < p.ne && !p.walk; c += 64) {
@@ -791,7 +775,7 @@ DEV void plan_doc_split(P &p, PlanResult *res) {
         top += uint32_t(__popcll(m));
     }
     if (__ballot(bad_np)) fail(p, PLAN_WIDE_MERGE);
-    wave_fence();
+    fence_wave();
     tk(p);
     PT(5);
     // ---- phase A: the order (walk_kernel's, when it ran) ----
@@ -844,7 +828,7 @@ DEV void plan_doc_split(P &p, PlanResult *res) {
     // each chain's dense-table slice, in LDS (the todo stack's space: phase A is done)
     uint32_t *sdoff = reinterpret_cast<uint32_t *>(p.todo);
     if (l <= p.A) sdoff[l] = p.doff[l];
-    wave_fence();
+    fence_wave();
     // ---- phase B: per step, lane = step ----
     const uint32_t A = p.A;
     const uint32_t rs = p.row_stride;
@@ -906,15 +890,15 @@ DEV void plan_doc_split(P &p, PlanResult *res) {
         if (!valid) total = nadv = 0;
         const uint32_t ncmd = valid ? (total ? 1u : 0u) + nop : 0u;
         // offsets: prefix sums over the chunk's steps
-        const uint32_t ic = wave_scan(ncmd), it = wave_scan(total);
+        const uint32_t ic = scan_incl(ncmd), it = scan_incl(total);
         const uint32_t co = p.nc + ic - ncmd, to0 = p.nt + it - total;
-        const uint32_t sum_c = bcast(ic, 63), sum_t = bcast(it, 63);
-        const uint32_t sum_adv = bcast(wave_scan(nadv), 63);
+        const uint32_t sum_c = rdl(ic, 63), sum_t = rdl(it, 63);
+        const uint32_t sum_adv = rdl(scan_incl(nadv), 63);
         PT(1);
         if (code) { err_step = i; err_code = code; }
         const u64 em = __ballot(code != 0);
         if (em) {   // the first failing step ends the walk, as plan_doc1 stops there
-            fail(p, bcast(code, first_lane(em)));
+            fail(p, rdl(code, ctz(em)));
             break;
         }
         if (uint64_t(p.nc) + sum_c > p.ccap) { fail(p, PLAN_CMDS_FULL); break; }
@@ -1027,11 +1011,11 @@ DEV void plan_doc_split(P &p, PlanResult *res) {
         PT(2);
         if (!p.count_only) {
             for (u64 bm = __ballot(big); bm; bm &= bm - 1) {   // the big steps, one at a time
-                const uint32_t j = first_lane(bm);
-                const uint32_t be = U(bcast(e, j)), bep = U(bcast(ep, j)), bhp = U(bcast(hp ? 1u : 0u, j));
-                const uint32_t bpc = U(bcast(p_chain, j)), bpv = U(bcast(p_seq0 + (p_end - p_start), j));
-                const uint32_t bto = U(bcast(to0, j)), bco = U(bcast(co, j)), btot = U(bcast(total, j));
-                const uint32_t bop0 = U(bcast(op0, j)), bnop = U(bcast(nop, j));
+                const uint32_t j = ctz(bm);
+                const uint32_t be = U(rdl(e, j)), bep = U(rdl(ep, j)), bhp = U(rdl(hp ? 1u : 0u, j));
+                const uint32_t bpc = U(rdl(p_chain, j)), bpv = U(rdl(p_seq0 + (p_end - p_start), j));
+                const uint32_t bto = U(rdl(to0, j)), bco = U(rdl(co, j)), btot = U(rdl(total, j));
+                const uint32_t bop0 = U(rdl(op0, j)), bnop = U(rdl(nop, j));
                 uint32_t cw = bco;
                 if (btot) {
                     if (l == 0) p.cmds[cw] = Cmd{CMD_TOG, bto, btot, 0};
@@ -1043,11 +1027,11 @@ DEV void plan_doc_split(P &p, PlanResult *res) {
                     const bool adv = to > from;
                     const uint32_t n = adv ? to - from : from - to;
                     const uint32_t src = (l < A ? sdoff[l] : 0u) + (adv ? from : to), fl = adv ? TL_ADV : 0u;
-                    const uint32_t off = wave_scan(n) - n;
+                    const uint32_t off = scan_incl(n) - n;
                     bool bad = false;
                     for (u64 am = __ballot(n != 0); am; am &= am - 1) {
-                        const uint32_t a = first_lane(am);
-                        const uint32_t o = U(bcast(off, a)), nn = U(bcast(n, a)), sa = U(bcast(src, a)), fa = U(bcast(fl, a));
+                        const uint32_t a = ctz(am);
+                        const uint32_t o = U(rdl(off, a)), nn = U(rdl(n, a)), sa = U(rdl(src, a)), fa = U(rdl(fl, a));
                         for (uint32_t u0 = 0; u0 < nn; u0 += 64 * kSplitCopyDepth) {   // loads in flight together
                             uint32_t v[kSplitCopyDepth];
 #pragma unroll
@@ -1076,7 +1060,7 @@ DEV void plan_doc_split(P &p, PlanResult *res) {
         p.nt += sum_t;
         p.n_adv += sum_adv;
         p.n_ret += sum_t - sum_adv;
-        last_e = U(bcast(e, min(63u, ns - 1 - c0)));
+        last_e = U(rdl(e, min(63u, ns - 1 - c0)));
     }
     (void)err_step;
     PT(3);
@@ -1167,7 +1151,7 @@ DEV void plan_entry(const PlanParams &Q) {
     p.prof = Q.prof;
     res->n_tip = 0;
     if (p.ne > Q.lds_entries) {
-        if (lane_id() == 0) res->status = PLAN_ERR_INTERNAL;
+        if (lane() == 0) res->status = PLAN_ERR_INTERNAL;
         return;
     }
 #ifndef DTGPU_PLAN_OLD
@@ -1208,7 +1192,7 @@ DEV void walk_wait_vm() { __builtin_amdgcn_s_waitcnt(0x0F70); }
 template <bool CSR>
 __global__ __launch_bounds__(64) void walk_kernel(PlanParams Q) {
     extern __shared__ __attribute__((aligned(16))) uint16_t wl16[];
-    const uint32_t l = lane_id(), g = l / WG, c = l % WG, base = g * WG;
+    const uint32_t l = lane(), g = l / WG, c = l % WG, base = g * WG;
     const uint32_t cap = Q.todo_cap ? Q.todo_cap : PLAN_TODO_CAP;   // stack slots (even)
     const uint32_t stride = cap + (Q.lds_entries + 1) / 2;   // u16 per group: stack, pending bytes
     uint16_t *todo = wl16 + g * stride;

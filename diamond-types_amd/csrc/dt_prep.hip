@@ -18,20 +18,16 @@
 #include <stdint.h>
 
 #include "dt_prep.hpp"
+#include "dt_wave.hpp"
 
 namespace dtgpu {
 namespace prep {
+using namespace wave;
 
-__device__ __forceinline__ uint32_t lane() { return __lane_id(); }
-__device__ __forceinline__ uint32_t rdl(uint32_t v, uint32_t l) {
-    return uint32_t(__builtin_amdgcn_readlane(int(v), int(l)));
-}
-__device__ __forceinline__ uint64_t ballot(bool p) { return __ballot(p); }
-__device__ __forceinline__ uint64_t lt_mask() { return (1ull << lane()) - 1ull; }
-__device__ __forceinline__ uint32_t popc(uint64_t m) { return uint32_t(__popcll(m)); }
-__device__ __forceinline__ uint32_t ctz(uint64_t m) { return uint32_t(__ffsll((unsigned long long)m) - 1); }
-__device__ __forceinline__ void wave_fence() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); }
-__device__ __forceinline__ uint32_t scan_incl(uint32_t v) {   // inclusive prefix sum over the wave
+// Prep's three scans (this one, scan_max_excl and scan_min_suffix below) are lane-permute loops, a
+// different instruction sequence from dt_wave.hpp's DPP scans: the kernels are timed, and changing
+// their scans belongs to a change that measures it.
+__device__ __forceinline__ uint32_t scan_incl_permute(uint32_t v) {   // inclusive prefix sum over the wave
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
         const uint32_t o = uint32_t(__shfl_up(int(v), d));
@@ -203,14 +199,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DTGPU_PREP_W
         for (uint32_t i0 = 0; i0 < ne; i0 += 64) {
             const uint32_t i = i0 + l;
             const uint32_t c = i < ne ? lfill[i] : 0;
-            const uint32_t inc = scan_incl(c);
+            const uint32_t inc = scan_incl_permute(c);
             if (i < ne) { coff[i] = carry + inc - c; lfill[i] = 0; }
             carry += rdl(inc, 63);
         }
         if (l == 0) coff[ne] = carry;
     }
     __syncthreads();
-    wave_fence();
+    fence_workgroup();
     // children in child-index order (slots are in (child, parent) order): a stable scatter,
 #ifdef DTGPU_PREP_PROF
     T1 = wall_clock64();
@@ -277,7 +273,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DTGPU_PREP_W
         }
         if (l == 0) eop[ne] = nops;
     }
-    wave_fence();
+    fence_workgroup();
     }   // P.mode != 2
     if (P.mode == 1) {   // first half done: chain_kernel (or the second half) goes on from HBM
         // each entry's children for the walk kernel, which starts now: {children | first slot
@@ -408,7 +404,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DTGPU_PREP_W
             if ((i & 63u) == 63u || i + 1 == ne) {
                 const uint32_t at = i & ~63u;
                 if (at + l <= i) cs[at + l] = make_uint2(bch, bsd);
-                wave_fence();   // later entries read these pairs back from other lanes
+                fence_workgroup();   // later entries read these pairs back from other lanes
             }
             prev_row = row; prev_chain = c; prev_sd = s0 - s;
             {
@@ -435,7 +431,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DTGPU_PREP_W
                    (unsigned long long)pk, (unsigned long long)pa, (unsigned long long)pb, (unsigned long long)pc_);
 #endif
     }
-    wave_fence();
+    fence_workgroup();
     if (report_oob()) return;
 #ifdef DTGPU_PREP_PROF
     const uint64_t T4 = wall_clock64();
@@ -446,7 +442,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DTGPU_PREP_W
         doff_l = l < nch ? doff[l] : 0u;   // (doff[PREP_MAX_CHAINS] holds the chain count)
     } else {
         const uint32_t c = l < nch ? clen : 0;
-        const uint32_t inc = scan_incl(c);
+        const uint32_t inc = scan_incl_permute(c);
         doff_l = inc - c;
         PREP_ASSERT(rdl(inc, 63) == D.n_lv, PREP_T_DOFF);   // the chains partition the LVs
         if (l < nch) doff[l] = doff_l;
@@ -481,7 +477,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DTGPU_PREP_W
             }
         }
     }
-    wave_fence();
+    fence_workgroup();
     // entry records (dt_host.hpp PlanInput::erec), one per lane: a lane's head (32 bytes) and
     // tail (48) are contiguous and next to its neighbours', so the stores coalesce as they are
     // (the 80-byte records of round 4 went through LDS, with a fence per 32 records).
@@ -737,7 +733,7 @@ __global__ __launch_bounds__(64) void chain_kernel(PrepParams P) {
         const bool on = ok && i < ne;
         const uint32_t ib = i & (G - 1), at = i & ~(G - 1);
         if (ib == 0) {
-            wave_fence();   // the block flushed in the middle of the last one is readable
+            fence_workgroup();   // the block flushed in the middle of the last one is readable
             if (on) {
                 const uint32_t j = min(i + c, ne - 1);
                 bk0 = poff[j];
@@ -807,7 +803,7 @@ __global__ __launch_bounds__(64) void chain_kernel(PrepParams P) {
         const uint32_t at = (ne - 1) & ~(G - 1);
         if (at && ((ne - 1) & (G - 1)) < FLUSH_AT) flush(at - G, at);
         flush(at, ne);
-        wave_fence();
+        fence_workgroup();
     }
     if (ok) {   // the chain tables' offsets: exclusive prefix of the chain lengths
         uint32_t v = c < nch ? clen : 0u;
@@ -838,7 +834,6 @@ __global__ __launch_bounds__(64) void chain_kernel(PrepParams P) {
 //   deletes not inside one range).
 // (the cut kernel's scratch is written by stores and memory-side atomics and read back by other
 // lanes: an agent-scope fence also drops the CU's L1 lines, so no read meets a stale one)
-__device__ __forceinline__ void agent_fence() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent"); }
 __device__ __forceinline__ uint32_t scan_max_excl(uint32_t v) {   // exclusive prefix max
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
@@ -917,7 +912,7 @@ __global__ __launch_bounds__(64 * CUT_WAVES) void cut_kernel(CutParams P) {
         suf[e] = mp;
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    agent_fence();
+    fence_agent();
     // 2. suffix minima of the smallest parents (suf[k] = over entries >= k; suf[ne] = none)
     {
         int32_t carry = 0x7FFFFFFF;
@@ -929,7 +924,7 @@ __global__ __launch_bounds__(64 * CUT_WAVES) void cut_kernel(CutParams P) {
         }
         if (l == 0) suf[ne] = 0x7FFFFFFF;
     }
-    agent_fence();
+    fence_agent();
     // 3. the cut ranges, compacted in entry order
     uint32_t nr = 0;
     {
@@ -957,7 +952,7 @@ __global__ __launch_bounds__(64 * CUT_WAVES) void cut_kernel(CutParams P) {
             carry = max(carry, cm);
         }
     }
-    agent_fence();
+    fence_agent();
     if (nr != 0) {
     auto in_cut = [&](uint32_t v) {
         const uint32_t i = range_of(rng, nr, v);
@@ -1052,7 +1047,7 @@ __global__ __launch_bounds__(64 * CUT_WAVES) void cut_kernel(CutParams P) {
             }
             const uint32_t rl = rdl(ri, min(b1 - 1 - c0, 63u));
             if (rl < nr) rc = rl;
-            const uint32_t si = scan_incl(vi), sd = scan_incl(vd), sc = scan_incl(vc);
+            const uint32_t si = scan_incl_permute(vi), sd = scan_incl_permute(vd), sc = scan_incl_permute(vc);
             while (pi < npick) {
                 const uint32_t pj = rdl(picks, pi);
                 if (pj >= c0 + 64 || pj >= b1) break;

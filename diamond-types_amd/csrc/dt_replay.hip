@@ -54,37 +54,15 @@
 #include <stdint.h>
 
 #include "dt_device.hpp"
+#include "dt_wave.hpp"
 
 namespace dtgpu {
 namespace dev {
+using namespace wave;
 
-typedef unsigned long long u64;
-
-#define DEV __device__ __forceinline__
-
-DEV uint32_t lane_id() { return __lane_id(); }
-DEV void wave_fence() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier(); }
-DEV uint32_t bcast(uint32_t v, uint32_t l) { return uint32_t(__builtin_amdgcn_readlane(int(v), int(l))); }
-DEV u64 bcast64(u64 v, uint32_t l) {
-    return (u64(bcast(uint32_t(v >> 32), l)) << 32) | u64(bcast(uint32_t(v), l));
-}
-DEV uint32_t first_lane(u64 m) { return uint32_t(__ffsll((long long)m) - 1); }
-DEV uint32_t last_lane(u64 m) { return 63u - uint32_t(__clzll((long long)m)); }
-// Wave-uniform values are pinned to scalar registers: control flow that depends on them is
-// scalar (no exec-mask loops), which is both what the algorithm means and what keeps hipcc
-// from treating the sequential replay as divergent.
-DEV uint32_t U(uint32_t v) { return uint32_t(__builtin_amdgcn_readfirstlane(int(v))); }
-DEV u64 U64(u64 v) {   // (readfirstlane returns int: keep both halves unsigned)
-    return (u64(U(uint32_t(v >> 32))) << 32) | u64(U(uint32_t(v)));
-}
-DEV uint32_t shfl(uint32_t v, uint32_t src) {
-    return uint32_t(__builtin_amdgcn_ds_bpermute(int(src << 2), int(v)));
-}
-DEV u64 lanes_below(uint32_t l) { return l >= 64 ? ~0ull : ((1ull << l) - 1ull); }
-// Set bits of m below this lane (v_mbcnt: two VALU ops, no 64-bit shifts).
-DEV uint32_t bits_below(u64 m) {
-    return __builtin_amdgcn_mbcnt_hi(uint32_t(m >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(m), 0u));
-}
+// The replay's flags are 0/1 integers (vflag, below), so its ballots take the integer as
+// __ballot does; wave::ballot's bool parameter compiles to a different instruction stream here.
+#define BALLOT(c) __ballot(c)
 // The replay's scalar issue is its bottleneck (one SALU per SIMD per 4 cycles; +48 SALU per
 // command costs the full issue time, +48 VALU 40 % of it): per-lane flags are kept as 0/1
 // integers in VGPRs.  A bool per lane is a lane mask in SGPRs, and each &&, || or ! on it is a
@@ -94,43 +72,6 @@ DEV uint32_t vflag(bool c) {
     asm volatile("" : "+v"(x));
     return x;
 }
-// __ballot with the mask straight from the compare (the HIP wrapper adds a select and a compare).
-#define BALLOT(c) __ballot(c)
-
-// Inclusive wave prefix sum over 64 lanes with DPP: Hillis-Steele inside each 16-lane row
-// (row_shr 1/2/4/8), then row_bcast:15 and row_bcast:31 carry the row totals forward.
-// Validated against a sequential prefix sum by tools/scan_probe.hip.
-DEV uint32_t wave_scan(uint32_t x) {
-    x += uint32_t(__builtin_amdgcn_update_dpp(0, int(x), 0x111, 0xF, 0xF, false));
-    x += uint32_t(__builtin_amdgcn_update_dpp(0, int(x), 0x112, 0xF, 0xF, false));
-    x += uint32_t(__builtin_amdgcn_update_dpp(0, int(x), 0x114, 0xF, 0xF, false));
-    x += uint32_t(__builtin_amdgcn_update_dpp(0, int(x), 0x118, 0xF, 0xF, false));
-    x += uint32_t(__builtin_amdgcn_update_dpp(0, int(x), 0x142, 0xA, 0xF, false));
-    x += uint32_t(__builtin_amdgcn_update_dpp(0, int(x), 0x143, 0xC, 0xF, false));
-    return x;
-}
-// The same over lanes 0..31 only (lanes 32..63 left partial): one DPP step fewer.
-DEV uint32_t wave_scan32(uint32_t x) {
-    x += uint32_t(__builtin_amdgcn_update_dpp(0, int(x), 0x111, 0xF, 0xF, false));
-    x += uint32_t(__builtin_amdgcn_update_dpp(0, int(x), 0x112, 0xF, 0xF, false));
-    x += uint32_t(__builtin_amdgcn_update_dpp(0, int(x), 0x114, 0xF, 0xF, false));
-    x += uint32_t(__builtin_amdgcn_update_dpp(0, int(x), 0x118, 0xF, 0xF, false));
-    x += uint32_t(__builtin_amdgcn_update_dpp(0, int(x), 0x142, 0xA, 0xF, false));
-    return x;
-}
-DEV uint32_t wave_sum(uint32_t v) { return uint32_t(__builtin_amdgcn_readlane(int(wave_scan(v)), 63)); }
-DEV u64 wave_sum64(u64 v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-DEV u64 splitmix(u64 z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-DEV uint32_t utf8_len(uint8_t c) { return c < 0x80 ? 1 : (c & 0xE0) == 0xC0 ? 2 : (c & 0xF0) == 0xE0 ? 3 : 4; }
 
 constexpr uint32_t BLK = 64;   // slots per block
 constexpr uint32_t SBC = 64;   // block capacity of a superblock list
@@ -316,8 +257,8 @@ template <int L> DEV uint32_t key_of(const Doc &D, uint32_t item) {
 // Same for a wave-uniform item: one row load and a ballot.
 template <int L> DEV uint32_t ukey_of(const Doc &D, uint32_t item) {
     const uint32_t b = U(pc_blk(ld(D.pc + item)));
-    const u64 m = BALLOT(D.items[size_t(b) * BLK + lane_id()] == item);
-    return U(key_at<L>(D, b, first_lane(m)));
+    const u64 m = BALLOT(D.items[size_t(b) * BLK + lane()] == item);
+    return U(key_at<L>(D, b, ctz(m)));
 }
 
 // Block holding visible index p and the rank k of that item among the block's visible items
@@ -330,18 +271,18 @@ struct Found {
 };
 template <int L>
 DEV bool find_vis(Doc &D, uint32_t p, Found &f) {
-    const uint32_t l = lane_id();
+    const uint32_t l = lane();
     uint32_t base = 0, S = NONE;
     if (L == IX_FLAT) {   // chunk totals, then the chunk's blocks
         const uint32_t nc = (D.nb + 63) >> 6;
         {   // at most 32 chunks (FLAT_MAX_BLOCKS): one scan over lanes 0..31
             const uint32_t w0 = D.top[min(l, nc - 1)];
             const uint32_t v = l < nc ? (w0 & 0xFFFFu) : 0u;
-            const uint32_t inc = wave_scan32(v);
+            const uint32_t inc = scan_incl32(v);
             const u64 m = BALLOT(inc > p) & 0xFFFFFFFFull;
             if (!m) return false;
-            S = first_lane(m);
-            base = bcast(inc - v, S);
+            S = ctz(m);
+            base = rdl(inc - v, S);
         }
         f.S = f.tp = S;
         const uint32_t q = (S << 6) + l;
@@ -349,13 +290,13 @@ DEV bool find_vis(Doc &D, uint32_t p, Found &f) {
         const uint32_t w = D.cnt[b0];
         const uint32_t b = q < D.nb ? b0 : 0;
         const uint32_t v = q < D.nb ? c_vis(w) : 0;
-        const uint32_t inc = wave_scan(v);
+        const uint32_t inc = scan_incl(v);
         const u64 m = BALLOT(base + inc > p);
         if (!m) return false;
-        const uint32_t fl = first_lane(m);
-        f.b = U(bcast(b, fl));
-        f.k = U(p - base - bcast(inc - v, fl));
-        f.c = U(bcast(w, fl));
+        const uint32_t fl = ctz(m);
+        f.b = U(rdl(b, fl));
+        f.k = U(p - base - rdl(inc - v, fl));
+        f.c = U(rdl(w, fl));
         return true;
     }
     for (uint32_t c = 0; c < D.nsb; c += 64) {
@@ -363,16 +304,16 @@ DEV bool find_vis(Doc &D, uint32_t p, Found &f) {
         const uint32_t w0 = ix<L>(D.top + min(i, D.nsb - 1));   // clamped, then masked: no exec branch
         const uint32_t w = i < D.nsb ? w0 : 0;
         const uint32_t v = w & 0xFFFFu;
-        const uint32_t inc = wave_scan(v);
+        const uint32_t inc = scan_incl(v);
         const u64 m = BALLOT(base + inc > p);
         if (m) {
-            const uint32_t fl = first_lane(m);
-            S = U(bcast(w, fl) >> 16);
+            const uint32_t fl = ctz(m);
+            S = U(rdl(w, fl) >> 16);
             f.tp = U(c + fl);
-            base += bcast(inc - v, fl);
+            base += rdl(inc - v, fl);
             break;
         }
-        base += bcast(inc, 63);
+        base += rdl(inc, 63);
     }
     if (S == NONE) return false;
     f.S = S;
@@ -382,28 +323,28 @@ DEV bool find_vis(Doc &D, uint32_t p, Found &f) {
     const uint32_t b = l < n ? b0 : 0;
     const uint32_t v0 = c_vis(ix<L>(D.cnt + b));
     const uint32_t v = l < n ? v0 : 0;
-    const uint32_t inc = wave_scan(v);
+    const uint32_t inc = scan_incl(v);
     const u64 m = BALLOT(base + inc > p);
     if (!m) return false;
-    const uint32_t fl = first_lane(m);
-    f.b = U(bcast(b, fl));
-    f.k = U(p - base - bcast(inc - v, fl));
+    const uint32_t fl = ctz(m);
+    f.b = U(rdl(b, fl));
+    f.k = U(p - base - rdl(inc - v, fl));
     return true;
 }
 
 // Slot of the k-th set bit of a wave-uniform mask.
 DEV uint32_t select_bit(u64 m, uint32_t k) {
-    const uint32_t l = lane_id();
+    const uint32_t l = lane();
     const bool set = (m >> l) & 1ull;
     const uint32_t before = uint32_t(__popcll(m & lanes_below(l)));
-    return first_lane(BALLOT(set && before == k));
+    return ctz(BALLOT(set && before == k));
 }
 
 // First block after b (document order) with a live item, or NONE (origin_right search,
 // merge.rs:405-423).
 template <int L>
 DEV uint32_t next_live_block(Doc &D, uint32_t b) {
-    const uint32_t l = lane_id();
+    const uint32_t l = lane();
     if (L == IX_FLAT) {
         const uint32_t p0 = U(D.opos16[b]) + 1, nc = (D.nb + 63) >> 6;
         uint32_t c = p0 >> 6;
@@ -414,7 +355,7 @@ DEV uint32_t next_live_block(Doc &D, uint32_t b) {
             const uint32_t bl = in ? b0 : 0;
             const uint32_t cl = c_live(D.cnt[bl]);
             const u64 m = BALLOT(in && cl != 0);
-            if (m) return U(bcast(bl, first_lane(m)));
+            if (m) return U(rdl(bl, ctz(m)));
         }
         for (c = c + 1; c < nc; c += 64) {   // later chunks by their live totals
             if (!charge(D)) return NONE;
@@ -422,13 +363,13 @@ DEV uint32_t next_live_block(Doc &D, uint32_t b) {
             const uint32_t t = D.top[min(i, nc - 1)] >> 16;
             const u64 m = BALLOT(i < nc && t != 0);
             if (m) {
-                const uint32_t q = ((c + first_lane(m)) << 6) + l;
+                const uint32_t q = ((c + ctz(m)) << 6) + l;
                 const uint32_t b0 = D.sbl[min(q, D.nb - 1)];
                 const uint32_t bl = q < D.nb ? b0 : 0;
                 const uint32_t cl = c_live(D.cnt[bl]);
                 const u64 m2 = BALLOT(q < D.nb && cl != 0);
                 if (!m2) { fail(D, ErrCheckout, 19); return NONE; }
-                return U(bcast(bl, first_lane(m2)));
+                return U(rdl(bl, ctz(m2)));
             }
         }
         return NONE;
@@ -441,7 +382,7 @@ DEV uint32_t next_live_block(Doc &D, uint32_t b) {
         const uint32_t bl = l < n ? b0 : 0;
         const uint32_t cl = c_live(ix<L>(D.cnt + bl));
         const u64 m = BALLOT(l >= i0 && l < n && cl != 0);
-        if (m) return U(bcast(bl, first_lane(m)));
+        if (m) return U(rdl(bl, ctz(m)));
     }
     for (uint32_t p = U(ix<L>(D.sbpos + S)) + 1; p < D.nsb; p += 64) {
         if (!charge(D)) return NONE;
@@ -449,14 +390,14 @@ DEV uint32_t next_live_block(Doc &D, uint32_t b) {
         const uint32_t tl = ix<L>(D.tlive + min(i, D.nsb - 1));
         const u64 m = BALLOT(i < D.nsb && tl != 0);
         if (m) {
-            S = U(ix<L>(D.top + p + first_lane(m)) >> 16);
+            S = U(ix<L>(D.top + p + ctz(m)) >> 16);
             const uint32_t n = U(ix<L>(D.sbn + S));
             const uint32_t b0 = ix16<L>(D.sbl + size_t(S) * SBC + l);
             const uint32_t bl = l < n ? b0 : 0;
             const uint32_t cl = c_live(ix<L>(D.cnt + bl));
             const u64 m2 = BALLOT(l < n && cl != 0);
             if (!m2) { fail(D, ErrCheckout, 19); return NONE; }
-            return U(bcast(bl, first_lane(m2)));
+            return U(rdl(bl, ctz(m2)));
         }
     }
     return NONE;
@@ -468,7 +409,7 @@ DEV uint32_t next_live_block(Doc &D, uint32_t b) {
 // it in the top order.
 template <int L, bool XF>
 DEV void split_sb(Doc &D, uint32_t S) {
-    const uint32_t l = lane_id();
+    const uint32_t l = lane();
     if (D.nsb >= D.max_sb) { fail(D, ErrCapacity, 21); return; }
     const uint32_t S2 = D.nsb;
     uint32_t vis = 0, live = 0, up = 0;
@@ -478,7 +419,7 @@ DEV void split_sb(Doc &D, uint32_t S) {
         vis = c_vis(c);
         live = c_live(c);
         up = c_up(c);
-        wave_fence();
+        fence_wave();
         if (l >= SBC / 2) {
             D.sbl[size_t(S2) * SBC + (l - SBC / 2)] = uint16_t(b);
             set_opos<L>(D, b, (S2 << 6) | (l - SBC / 2));
@@ -493,12 +434,12 @@ DEV void split_sb(Doc &D, uint32_t S) {
         const int i = c - int(l);
         uint32_t w = 0, lv = 0, uv = 0;
         if (i >= int(p)) { w = ix<L>(D.top + i); lv = ix<L>(D.tlive + i); if (XF) uv = ix<L>(D.tup + i); }
-        wave_fence();
+        fence_wave();
         if (i >= int(p)) {
             D.top[i + 1] = w; D.tlive[i + 1] = lv; D.sbpos[w >> 16] = uint32_t(i + 1);
             if (XF) D.tup[i + 1] = uv;
         }
-        wave_fence();
+        fence_wave();
     }
     if (l == 0) {
         D.sbn[S] = SBC / 2;
@@ -508,7 +449,7 @@ DEV void split_sb(Doc &D, uint32_t S) {
         D.sbpos[S2] = p;
         if (XF) { D.tup[p - 1] = ul; D.tup[p] = uh; }
     }
-    wave_fence();
+    fence_wave();
     D.nsb++;
 }
 
@@ -516,7 +457,7 @@ DEV void split_sb(Doc &D, uint32_t S) {
 // move to a new block b2 placed right after b in its superblock.
 template <int L, bool XF>
 DEV uint32_t split_block(Doc &D, uint32_t b, uint32_t c, uint32_t it, u64 mv, u64 ml) {
-    const uint32_t l = lane_id();
+    const uint32_t l = lane();
     if (D.nb >= D.max_blocks) { fail(D, ErrCapacity, 12); return 0; }
     const uint32_t b2 = D.nb;
     u64 mu = 0, mu_lo = 0, mu_hi = 0;
@@ -542,7 +483,7 @@ DEV uint32_t split_block(Doc &D, uint32_t b, uint32_t c, uint32_t it, u64 mv, u6
             const bool mvl = q > int(pos);
             uint32_t v = 0;
             if (mvl) v = D.sbl[q];
-            wave_fence();
+            fence_wave();
             if (mvl) {
                 D.sbl[q + 1] = uint16_t(v);
                 D.opos16[v] = uint16_t(q + 1);
@@ -553,7 +494,7 @@ DEV uint32_t split_block(Doc &D, uint32_t b, uint32_t c, uint32_t it, u64 mv, u6
                     at_add(D.top + (uint32_t(q + 1) >> 6), w);
                 }
             }
-            wave_fence();
+            fence_wave();
         }
         if (l == 0) {
             const uint32_t v2 = uint32_t(__popcll(mv_hi)), l2 = uint32_t(__popcll(ml_hi));
@@ -567,7 +508,7 @@ DEV uint32_t split_block(Doc &D, uint32_t b, uint32_t c, uint32_t it, u64 mv, u6
                 at_add(D.top + ((pos + 1) >> 6), w);
             }
         }
-        wave_fence();
+        fence_wave();
         D.nb++;
         return b2;
     }
@@ -577,7 +518,7 @@ DEV uint32_t split_block(Doc &D, uint32_t b, uint32_t c, uint32_t it, u64 mv, u6
         uint32_t v = 0;
         const bool mv_lane = l > i && l < n;
         if (mv_lane) v = ix16<L>(D.sbl + size_t(S) * SBC + l);
-        wave_fence();
+        fence_wave();
         if (mv_lane) {
             D.sbl[size_t(S) * SBC + l + 1] = uint16_t(v);
             set_opos<L>(D, v, (S << 6) | (l + 1));
@@ -593,7 +534,7 @@ DEV uint32_t split_block(Doc &D, uint32_t b, uint32_t c, uint32_t it, u64 mv, u6
         set_opos<L>(D, b2, (S << 6) | (i + 1));
         D.sbn[S] = n + 1;
     }
-    wave_fence();
+    fence_wave();
     D.nb++;
     if (n + 1 == SBC) split_sb<L, XF>(D, S);
     return b2;
@@ -613,7 +554,7 @@ template <int L> DEV uint32_t cut_point(uint32_t s) { return L ? min(max(s, 16u)
 // integrate() / apply() report as BaseMoved, merge.rs:154-278, 457-556).
 template <int L>
 DEV uint32_t up_rank(Doc &D, uint32_t b, uint32_t s) {
-    const uint32_t l = lane_id();
+    const uint32_t l = lane();
     const uint32_t o = U(opos_of<L>(D, b));
     const uint32_t S = o >> 6, i = o & 63u, tp = U(ix<L>(D.sbpos + S));
     uint32_t r = 0;
@@ -630,7 +571,7 @@ template <int L, bool PROF, bool XF>
 DEV void insert_run(Doc &D, uint32_t b, uint32_t s, uint32_t it, u64 mv, u64 ml, uint32_t lv, uint32_t k,
                     uint32_t ol, uint32_t orr, uint32_t tph, uint32_t c_in) {
     D.cb = NONE;
-    const uint32_t l = lane_id();
+    const uint32_t l = lane();
     const uint32_t lv0 = lv, k0 = k;
     if (XF) {   // the run's items land at consecutive upstream positions
         const uint32_t r0 = up_rank<L>(D, b, s);
@@ -658,7 +599,7 @@ DEV void insert_run(Doc &D, uint32_t b, uint32_t s, uint32_t it, u64 mv, u64 ml,
             }
         }
         if (l < k) D.ao[lv + l] = u64(l == 0 ? ol : lv + l - 1) | (u64(orr) << 32);
-        wave_fence();
+        fence_wave();
         D.cb = b; D.cit = it; D.cmv = mv; D.cml = ml;
         return;
     }
@@ -718,7 +659,7 @@ DEV void insert_run(Doc &D, uint32_t b, uint32_t s, uint32_t it, u64 mv, u64 ml,
             }
             if (XF) at_add(D.tup + tp, m);
         }
-        wave_fence();
+        fence_wave();
         if (PROF) { const uint64_t t = tick<PROF>(); D.prof[P_R2] += t - tr; tr = t; }
         lv += m;
         k -= m;
@@ -736,7 +677,7 @@ DEV void insert_run(Doc &D, uint32_t b, uint32_t s, uint32_t it, u64 mv, u64 ml,
 // YjsMod tie-break key of an LV: (agent name rank, seq) (merge.rs:199-218).  64-ary search
 // over the agent runs; `lv` is wave-uniform.
 DEV void agent_of(Doc &D, uint32_t lv, uint32_t &rank, uint32_t &seq) {
-    const uint32_t l = lane_id();
+    const uint32_t l = lane();
     const GLOBAL_AS uint32_t *aruns = gp(vld(&KP().aruns)) + U(uint32_t(vld(&D.desc->arun_off)));
     uint32_t lo = 0, n = U(vld(&D.desc->n_aruns));   // last run with start <= lv lies in [lo, lo+n)
     while (n > 64) {
@@ -764,7 +705,7 @@ DEV void agent_of(Doc &D, uint32_t lv, uint32_t &rank, uint32_t &seq) {
 template <int L>
 DEV void yjs_scan(Doc &D, uint32_t &b, uint32_t &s, uint32_t rb, uint32_t rs, uint32_t my_l, uint32_t my_r,
                   uint32_t ol_new, uint32_t orr_new, uint32_t lv) {
-    const uint32_t l = lane_id();
+    const uint32_t l = lane();
     uint32_t new_rank, new_seq;
     agent_of(D, lv, new_rank, new_seq);
     bool scanning = false;
@@ -810,9 +751,9 @@ DEV void yjs_scan(Doc &D, uint32_t &b, uint32_t &s, uint32_t rb, uint32_t rs, ui
         const bool tie = inr && kl == my_l && orr_o == orr_new;
         bool new_lt = false;
         for (u64 mt = BALLOT(tie); mt; mt &= mt - 1) {
-            const uint32_t f = first_lane(mt);
+            const uint32_t f = ctz(mt);
             uint32_t r2, s2;
-            agent_of(D, U(bcast(o, f)), r2, s2);
+            agent_of(D, U(rdl(o, f)), r2, s2);
             const bool lt = new_rank < r2 || (new_rank == r2 && new_seq < s2);
             if (l == f) new_lt = lt;
         }
@@ -820,7 +761,7 @@ DEV void yjs_scan(Doc &D, uint32_t &b, uint32_t &s, uint32_t rb, uint32_t rs, ui
         const bool setv = inr && kl == my_l && orr_o != orr_new && kr < my_r;
         const bool clr = inr && kl == my_l && !stop && !setv;
         const u64 ms = BALLOT(stop);
-        const uint32_t lim = ms ? first_lane(ms) : end;
+        const uint32_t lim = ms ? ctz(ms) : end;
         const u64 below = lanes_below(lim);
         const u64 mset = BALLOT(setv) & below, mclr = BALLOT(clr) & below;
         if (mset | mclr) {
@@ -828,7 +769,7 @@ DEV void yjs_scan(Doc &D, uint32_t &b, uint32_t &s, uint32_t rb, uint32_t rs, ui
             const int ls = mset ? int(last_lane(mset)) : -1;
             if (ls > lc) {
                 const u64 after = lc >= 0 ? (mset & ~((2ull << lc) - 1ull)) : mset;
-                if (lc >= 0 || !scanning) { scanning = true; st_b = cb; st_s = first_lane(after); }
+                if (lc >= 0 || !scanning) { scanning = true; st_b = cb; st_s = ctz(after); }
             } else {
                 scanning = false;
             }
@@ -847,7 +788,7 @@ DEV void yjs_scan(Doc &D, uint32_t &b, uint32_t &s, uint32_t rb, uint32_t rs, ui
 // rebuilt from the items' counts and stored back clean.
 template <int L, bool PROF = false>
 DEV void load_block(Doc &D, uint32_t b, uint32_t c, uint32_t &it, u64 &mv, u64 &ml) {
-    const uint32_t l = lane_id();
+    const uint32_t l = lane();
     const uint32_t bc = c_items(c);
     if (PROF) { D.prof[P_N_LOAD]++; if (c & C_DIRTY) D.prof[P_N_DIRTY]++; }
     const uint32_t it0 = D.items[size_t(b) * BLK + l];   // the row holds BLK slots
@@ -858,11 +799,11 @@ DEV void load_block(Doc &D, uint32_t b, uint32_t c, uint32_t &it, u64 &mv, u64 &
         ml = BALLOT(l < bc && k != 0u);
         st(D.m2 + 2 * size_t(b) + (l & 1u), (l & 1u) ? ml : mv);
         if (l == 0) D.cnt[b] = c & ~C_DIRTY;
-        wave_fence();
+        fence_wave();
     } else {
         const u64 x = ld(D.m2 + 2 * size_t(b) + (l & 1u));
-        mv = bcast64(x, 0);
-        ml = bcast64(x, 1);
+        mv = rdl64(x, 0);
+        ml = rdl64(x, 1);
     }
 }
 
@@ -895,7 +836,7 @@ DEV void do_insert(Doc &D, uint32_t lv, uint32_t k, uint32_t pos) {
     if (pos) {
         const uint32_t s0 = select_bit(mv, kk);
         if (s0 >= bc) { fail(D, ErrCheckout, 13); return; }
-        ol = U(bcast(it, s0));
+        ol = U(rdl(it, s0));
         s = s0 + 1;
     }
     if (PROF) { const uint64_t t = tick<PROF>(); D.prof[P_BLOAD] += t - tp; tp = t; }
@@ -905,8 +846,8 @@ DEV void do_insert(Doc &D, uint32_t lv, uint32_t k, uint32_t pos) {
     bool direct;
     if (mlr) {
         rb = b;
-        rs = first_lane(mlr);
-        orr = U(bcast(it, rs));
+        rs = ctz(mlr);
+        orr = U(rdl(it, rs));
         direct = rs == s;
     } else {
         rb = next_live_block<L>(D, b);
@@ -915,8 +856,8 @@ DEV void do_insert(Doc &D, uint32_t lv, uint32_t k, uint32_t pos) {
             uint32_t rit;
             u64 rmv, rml;
             load_block<L, PROF>(D, rb, U(ix<L>(D.cnt + rb)), rit, rmv, rml);
-            rs = first_lane(rml);
-            orr = U(bcast(rit, rs));
+            rs = ctz(rml);
+            orr = U(rdl(rit, rs));
         } else {
             rs = 0;
             orr = END_ID;
@@ -953,7 +894,7 @@ DEV void do_insert(Doc &D, uint32_t lv, uint32_t k, uint32_t pos) {
 // the j-th item (fwd) or the (n-1-j)-th item (reversed / backspace runs, op_metrics.rs:184-202).
 template <int L, bool PROF, bool XF>
 DEV void do_delete(Doc &D, uint32_t lv, uint32_t n, uint32_t pos, bool fwd) {
-    const uint32_t l = lane_id();
+    const uint32_t l = lane();
     uint32_t j0 = 0;
     uint32_t up_done = 0;   // XF: never-deleted items this run deleted in earlier (left) blocks
     while (j0 < n) {   // each round deletes >= 1 item or fails
@@ -1004,7 +945,7 @@ DEV void do_delete(Doc &D, uint32_t lv, uint32_t n, uint32_t pos, bool fwd) {
                 D.tup[tpos] = ix<L>(D.tup + tpos) - gone;
             }
         }
-        wave_fence();
+        fence_wave();
         D.cb = b; D.cit = it; D.cmv = mv & ~selm; D.cml = ml;
         j0 += take;
     }
@@ -1019,7 +960,7 @@ DEV void do_delete(Doc &D, uint32_t lv, uint32_t n, uint32_t pos, bool fwd) {
 // DIRTY; their masks are rebuilt when a command next loads them.
 template <int L, bool PROF>
 DEV void toggle_pass(Doc &D, uint32_t off, uint32_t n, uint32_t pre, bool have_pre) {
-    const uint32_t l = lane_id();
+    const uint32_t l = lane();
     uint64_t tq = tick<PROF>();
     // Software pipeline over the 64-entry chunks: the entry list and the delete targets are
     // read-only here, so chunk j + 1's entries and targets are fetched while chunk j's counts
@@ -1082,14 +1023,14 @@ DEV void toggle_pass(Doc &D, uint32_t off, uint32_t n, uint32_t pre, bool have_p
             dup = mn == 0u;
         }
         for (u64 dm = BALLOT(act && dup); dm;) {   // each round retires >= 1 lane
-            const uint32_t t = bcast(item, first_lane(dm));
+            const uint32_t t = rdl(item, ctz(dm));
             const u64 same = BALLOT(act && item == t);
             if (__popcll(same) > 1) {
                 const bool mine = (same >> l) & 1ull;
                 const int32_t sum = int32_t(wave_sum(mine ? uint32_t(d) : 0u));
                 const int32_t neg = int32_t(wave_sum(mine ? uint32_t(dneg) : 0u));
                 if (mine) {
-                    if (l == first_lane(same)) { d = sum; dneg = neg; }
+                    if (l == ctz(same)) { d = sum; dneg = neg; }
                     else act = false;
                 }
             }
@@ -1132,8 +1073,8 @@ DEV void toggle_pass(Doc &D, uint32_t off, uint32_t n, uint32_t pre, bool have_p
             }
         } else {   // HBM index: one atomic per distinct block (a global atomic is a memory-side request)
             for (u64 pend = BALLOT(flip); pend;) {   // each round retires >= 1 lane
-                const uint32_t f = first_lane(pend);
-                const uint32_t bb = bcast(b, f);
+                const uint32_t f = ctz(pend);
+                const uint32_t bb = rdl(b, f);
                 const u64 same = BALLOT(flip && b == bb);
                 const bool mine = (same >> l) & 1ull;
                 const uint32_t sv = wave_sum(mine ? uint32_t(dv) : 0u), sl = wave_sum(mine ? uint32_t(dl) : 0u);
@@ -1149,7 +1090,7 @@ DEV void toggle_pass(Doc &D, uint32_t off, uint32_t n, uint32_t pre, bool have_p
         }
         if (PROF) { const uint64_t t = tick<PROF>(); D.prof[P_T3] += t - tq; tq = t; }
     }
-    wave_fence();
+    fence_wave();
 }
 
 // The same pass for n <= 64 entries (every pass of a friendsforever document: 14 entries on
@@ -1160,7 +1101,7 @@ DEV void toggle_pass(Doc &D, uint32_t off, uint32_t n, uint32_t pre, bool have_p
 // DIRTY bits, the chunk / superblock totals and D.cb.
 template <int L, bool PROF>
 DEV void toggle_pass_1(Doc &D, uint32_t off, uint32_t n, uint32_t pre, bool have_pre) {
-    const uint32_t l = lane_id();
+    const uint32_t l = lane();
     uint64_t tq = tick<PROF>();
     if (n == 0) return;
     const uint32_t e = have_pre ? pre : D.tlist[off + min(l, n - 1)];
@@ -1196,14 +1137,14 @@ DEV void toggle_pass_1(Doc &D, uint32_t off, uint32_t n, uint32_t pre, bool have
             dup = mn == 0u;
         }
         for (u64 dm = BALLOT(act && dup); dm;) {   // each round retires >= 1 lane
-            const uint32_t t = bcast(item, first_lane(dm));
+            const uint32_t t = rdl(item, ctz(dm));
             const u64 same = BALLOT(act && item == t);
             if (__popcll(same) > 1) {
                 const bool mine = (same >> l) & 1ull;
                 const int32_t sum = int32_t(wave_sum(mine ? uint32_t(d) : 0u));
                 const int32_t neg = int32_t(wave_sum(mine ? uint32_t(dneg) : 0u));
                 if (mine) {
-                    if (l == first_lane(same)) { d = sum; dneg = neg; }
+                    if (l == ctz(same)) { d = sum; dneg = neg; }
                     else act = false;
                 }
             }
@@ -1243,8 +1184,8 @@ DEV void toggle_pass_1(Doc &D, uint32_t off, uint32_t n, uint32_t pre, bool have
         }
     } else {   // HBM index: one atomic per distinct block (a global atomic is a memory-side request)
         for (u64 pend = BALLOT(flip); pend;) {   // each round retires >= 1 lane
-            const uint32_t f = first_lane(pend);
-            const uint32_t bb = bcast(b, f);
+            const uint32_t f = ctz(pend);
+            const uint32_t bb = rdl(b, f);
             const u64 same = BALLOT(flip && b == bb);
             const bool mine = (same >> l) & 1ull;
             const uint32_t sv = wave_sum(mine ? uint32_t(dv) : 0u), sl = wave_sum(mine ? uint32_t(dl) : 0u);
@@ -1259,7 +1200,7 @@ DEV void toggle_pass_1(Doc &D, uint32_t off, uint32_t n, uint32_t pre, bool have
         }
     }
     if (PROF) { const uint64_t t = tick<PROF>(); D.prof[P_T3] += t - tq; tq = t; }
-    wave_fence();
+    fence_wave();
 }
 
 // Multi-wave retreat / advance pass (the big LDS tiers' workgroups have TOG_WAVES waves; the
@@ -1280,7 +1221,7 @@ constexpr uint32_t TOG_MW_MIN = DTGPU_TOG_MW_MIN;   // entries: shorter passes s
 __shared__ uint32_t tog_job[4];        // {off, n, go (0: the document is done), error}
 template <int L>
 DEV void toggle_chunks(Doc &D, uint32_t off, uint32_t n, uint32_t w0) {
-    const uint32_t l = lane_id();
+    const uint32_t l = lane();
     uint32_t err = 0;
     // the next chunk's entries and delete targets are fetched before this chunk's atomics
     auto fetch = [&](uint32_t j, uint32_t &e, uint32_t &tgt) {
@@ -1322,7 +1263,7 @@ DEV void toggle_chunks(Doc &D, uint32_t off, uint32_t n, uint32_t w0) {
 // The replay wave's side: post the pass, take its share, wait for the others.
 template <int L>
 DEV void toggle_mw(Doc &D, uint32_t off, uint32_t n) {
-    if (lane_id() == 0) { tog_job[0] = off; tog_job[1] = n; tog_job[2] = 1; tog_job[3] = 0; }
+    if (lane() == 0) { tog_job[0] = off; tog_job[1] = n; tog_job[2] = 1; tog_job[3] = 0; }
     __syncthreads();
     toggle_chunks<L>(D, off, n, 0);
     __syncthreads();
@@ -1348,7 +1289,7 @@ DEV void toggle_helper(Doc &D, uint32_t w) {
 template <int L>
 DEV void materialise(Doc &D, GLOBAL_AS uint8_t *out, uint32_t cap, uint32_t &len_out, u64 &hash_out, uint32_t &items_out) {
     constexpr uint32_t G = 8;
-    const uint32_t l = lane_id();
+    const uint32_t l = lane();
     const GLOBAL_AS uint32_t *cbyte = gp(vld(&KP().cbyte)) + vld(&D.desc->lv_off);
     const GLOBAL_AS uint8_t *content = gp(vld(&KP().content)) + vld(&D.desc->content_off);
     const bool ascii = U(vld(&D.desc->ascii)) != 0;
@@ -1376,8 +1317,8 @@ DEV void materialise(Doc &D, GLOBAL_AS uint8_t *out, uint32_t cap, uint32_t &len
             bool vis[G];
 #pragma unroll
             for (uint32_t g = 0; g < G; g++) {
-                const uint32_t b = bcast(bl, g);
-                vis[g] = l < bcast(nl, g);
+                const uint32_t b = rdl(bl, g);
+                vis[g] = l < rdl(nl, g);
                 const uint32_t i0 = D.items[size_t(b) * BLK + l];   // the row holds BLK slots
                 it[g] = vis[g] ? i0 : 0;
             }
@@ -1396,26 +1337,26 @@ DEV void materialise(Doc &D, GLOBAL_AS uint8_t *out, uint32_t cap, uint32_t &len
 #pragma unroll
                 for (uint32_t g = 0; g < G; g++) {
                     const uint32_t c = vis[g] ? 1u : 0u;
-                    const uint32_t inc = wave_scan(c);
+                    const uint32_t inc = scan_incl(c);
                     const uint32_t at = total + inc - c;
                     if (c) {
                         if (at < cap) out[at] = by[g];
                         h += splitmix((u64(at) << 8) | by[g]);
                     }
-                    total += bcast(inc, 63);
+                    total += rdl(inc, 63);
                 }
             } else {
 #pragma unroll
                 for (uint32_t g = 0; g < G; g++) {
                     const uint32_t c = vis[g] ? utf8_len(content[cb[g]]) : 0u;
-                    const uint32_t inc = wave_scan(c);
+                    const uint32_t inc = scan_incl(c);
                     const uint32_t at = total + inc - c;
                     for (uint32_t k = 0; k < c; k++) {
                         const uint8_t byte = content[cb[g] + k];
                         if (at + k < cap) out[at + k] = byte;
                         h += splitmix((u64(at + k) << 8) | byte);
                     }
-                    total += bcast(inc, 63);
+                    total += rdl(inc, 63);
                 }
             }
         }
@@ -1452,7 +1393,7 @@ DEV uint32_t first_apply_lv(const Cmd *cmds, uint32_t ncmd, uint32_t i) {
 // command of an entry below the cut precedes every command of an entry above it, and "the first
 // apply command at or after i has lv >= v" is monotone in i (64-ary search).
 DEV uint32_t seg_cmd(const Cmd *cmds, uint32_t ncmd, uint32_t v) {
-    const uint32_t l = lane_id();
+    const uint32_t l = lane();
     uint32_t lo = 0, hi = ncmd;   // answer in [lo, hi]
     while (lo < hi) {
         const uint32_t step = max(1u, (hi - lo + 63) / 64), b = lo;
@@ -1460,7 +1401,7 @@ DEV uint32_t seg_cmd(const Cmd *cmds, uint32_t ncmd, uint32_t v) {
         const bool in = i < hi;
         const u64 m = BALLOT(in && first_apply_lv(cmds, ncmd, i) >= v);
         if (m) {
-            const uint32_t f = first_lane(m);
+            const uint32_t f = ctz(m);
             hi = b + f * step;
             lo = f ? b + (f - 1) * step + 1 : b;
         } else {
@@ -1475,7 +1416,7 @@ DEV uint32_t seg_cmd(const Cmd *cmds, uint32_t ncmd, uint32_t v) {
 DEV bool seg_straddles(const Cmd *cmds, uint32_t c, uint32_t v) {
     if (v == NONE || c == 0) return false;
     bool bad = false;
-    if (lane_id() == 0) {
+    if (lane() == 0) {
         for (uint32_t j = c; j-- > 0;) {
             const Cmd x = cmds[j];
             if ((x.op & 15u) != CMD_TOG) { bad = x.lv + x.len > v; break; }
@@ -1488,7 +1429,7 @@ constexpr uint32_t PH_SB = 40;     // placeholder blocks per superblock
 // The tracker a segment starts from: u visible placeholder items in document order.
 template <int L>
 DEV bool init_phantoms(Doc &D, uint32_t u) {
-    const uint32_t l = lane_id();
+    const uint32_t l = lane();
     const uint32_t base = U(vld(&D.desc->n_lv));   // placeholder ids follow the LVs
     const uint32_t nbp = (u + PH_FILL - 1) / PH_FILL, nsb = (nbp + PH_SB - 1) / PH_SB;
     if (nbp + 1 > D.max_blocks || (L != IX_FLAT && nsb + 1 > D.max_sb)) { fail(D, ErrCapacity, 12); return false; }
@@ -1529,7 +1470,7 @@ DEV bool init_phantoms(Doc &D, uint32_t u) {
         D.items[size_t(b) * BLK + l] = l < k ? base + b * PH_FILL + l : 0u;
     }
     for (uint32_t p = l; p < u; p += 64) st(D.pc + base + p, pc_of(p / PH_FILL, 1u));
-    wave_fence();
+    fence_wave();
     D.nb = nbp;
     D.nsb = nsb;
     return true;
@@ -1539,7 +1480,7 @@ DEV bool init_phantoms(Doc &D, uint32_t u) {
 template <int L>
 DEV void materialise_src(Doc &D, GLOBAL_AS uint32_t *src, uint32_t cap, uint32_t &len_out, uint32_t &items_out) {
     constexpr uint32_t G = 8;
-    const uint32_t l = lane_id();
+    const uint32_t l = lane();
     const uint32_t n_lv = U(vld(&D.desc->n_lv));   // D.n_lv also counts the placeholders
     uint32_t total = 0, items = 0;
     const uint32_t nlists = L == IX_FLAT ? 1u : D.nsb;   // the flat index is one list
@@ -1563,8 +1504,8 @@ DEV void materialise_src(Doc &D, GLOBAL_AS uint32_t *src, uint32_t cap, uint32_t
             bool vis[G];
 #pragma unroll
             for (uint32_t g = 0; g < G; g++) {
-                const uint32_t b = bcast(bl, g);
-                vis[g] = l < bcast(nl, g);
+                const uint32_t b = rdl(bl, g);
+                vis[g] = l < rdl(nl, g);
                 const uint32_t i0 = D.items[size_t(b) * BLK + l];
                 it[g] = vis[g] ? i0 : 0;
             }
@@ -1573,10 +1514,10 @@ DEV void materialise_src(Doc &D, GLOBAL_AS uint32_t *src, uint32_t cap, uint32_t
 #pragma unroll
             for (uint32_t g = 0; g < G; g++) {
                 const uint32_t c = vis[g] ? 1u : 0u;
-                const uint32_t inc = wave_scan(c);
+                const uint32_t inc = scan_incl(c);
                 const uint32_t at = total + inc - c;
                 if (c && at < cap) src[at] = it[g] < n_lv ? it[g] : (SEG_PHANTOM | (it[g] - n_lv));
-                total += bcast(inc, 63);
+                total += rdl(inc, 63);
             }
         }
     }
@@ -1589,7 +1530,7 @@ DEV void materialise_src(Doc &D, GLOBAL_AS uint32_t *src, uint32_t cap, uint32_t
 // and that pos[] names each item's block.
 template <int L, bool XF>
 DEV uint32_t check_invariants(Doc &D, DocResult *res) {
-    const uint32_t l = lane_id();
+    const uint32_t l = lane();
     const uint32_t n_ids = D.n_lv;   // LVs, then a segment's placeholders
     uint32_t blocks = 0;
     const uint32_t nlists = L == IX_FLAT ? (D.nb + 63) >> 6 : D.nsb;   // flat: chunks of 64 positions
@@ -1637,7 +1578,7 @@ DEV uint32_t check_invariants(Doc &D, DocResult *res) {
             } else if (((mv | ml) >> l) & 1) bad = true;
             const u64 bm = BALLOT(bad);
             if (bm) {
-                if (l == first_lane(bm)) {
+                if (l == ctz(bm)) {
                     res->dbg[0] = b; res->dbg[1] = l; res->dbg[2] = cnt; res->dbg[3] = it; res->dbg[4] = w;
                     res->dbg[5] = uint32_t(mv); res->dbg[6] = uint32_t(mv >> 32);
                     res->dbg[7] = uint32_t(ml); res->dbg[8] = uint32_t(ml >> 32);
@@ -1660,7 +1601,7 @@ DEV uint32_t check_invariants(Doc &D, DocResult *res) {
 
 template <int L, bool PROF, bool XF, bool MW>
 DEV void run_doc(Doc &D) {
-    const uint32_t l = lane_id();
+    const uint32_t l = lane();
     D.nb = 1;
     D.nsb = 1;
     D.err = 0;
@@ -1689,7 +1630,7 @@ DEV void run_doc(Doc &D) {
             if (XF) { D.tup[0] = 0; st(D.mup, 0ull); }
         }
         if (l < 2) st(D.m2 + l, 0ull);
-        wave_fence();
+        fence_wave();
     }
     D.cb = NONE;
     D.cit = 0;
@@ -1714,15 +1655,15 @@ DEV void run_doc(Doc &D) {
         const u64 bad_cmds = BALLOT(l < n_here && (op_l > CMD_TOG || (apply_l && (pre.len == 0 || pre.lv >= D.n_lv ||
                                                                                pre.len > D.n_lv - pre.lv))));
         const u64 tog_cmds = BALLOT(l < n_here && op_l == CMD_TOG);
-        const uint32_t n_ok = bad_cmds ? first_lane(bad_cmds) : n_here;
+        const uint32_t n_ok = bad_cmds ? ctz(bad_cmds) : n_here;
         for (uint32_t j = 0; j < n_ok && !D.err; j++) {
             ci = base + j;
-            const uint32_t op = U(bcast(pre.op, j)), a = U(bcast(pre.lv, j)), n = U(bcast(pre.len, j)),
-                           pos = U(bcast(pre.pos, j));
+            const uint32_t op = U(rdl(pre.op, j)), a = U(rdl(pre.lv, j)), n = U(rdl(pre.len, j)),
+                           pos = U(rdl(pre.pos, j));
             uint32_t nx_pf = 0;
             bool nx_ok = false;
             if ((tog_cmds >> j) & 2ull) {   // the next command is a pass: its first entries now
-                const uint32_t o2 = U(bcast(pre.lv, j + 1)), n2 = U(bcast(pre.len, j + 1));
+                const uint32_t o2 = U(rdl(pre.lv, j + 1)), n2 = U(rdl(pre.len, j + 1));
                 if (n2) nx_pf = D.tlist[o2 + min(l, n2 - 1)];
                 nx_ok = true;
             }
@@ -1748,7 +1689,7 @@ DEV void run_doc(Doc &D) {
         }
         if (bad_cmds && !D.err) {
             ci = base + n_ok;
-            fail(D, ErrCheckout, (U(bcast(pre.op, n_ok)) & 15u) > CMD_TOG ? 18u : 17u);
+            fail(D, ErrCheckout, (U(rdl(pre.op, n_ok)) & 15u) > CMD_TOG ? 18u : 17u);
         }
     }
     // an LDS-tier document that outgrew its optimistic block capacity is queued for the HBM
@@ -1885,7 +1826,7 @@ __global__ __launch_bounds__(MW ? 64 * TOG_WAVES : 64) __attribute__((amdgpu_wav
     }
     run_doc<LDS_INDEX, PROF, XF, MW>(D);
     if (MW) {   // release the helper waves
-        if (lane_id() == 0) tog_job[2] = 0;
+        if (lane() == 0) tog_job[2] = 0;
         __syncthreads();
     }
 }
@@ -1965,7 +1906,7 @@ __global__ __launch_bounds__(COMBINE_THREADS) void combine_kernel(CombineParams 
             if (c < clen) { cb = c; len = ascii ? 1u : utf8_len(content[c]); }
             else s_bad = 1;
         }
-        const uint32_t inc = wave_scan(len);
+        const uint32_t inc = scan_incl(len);
         if ((t & 63) == 63) s_wsum[w] = inc;
         __syncthreads();
         uint32_t before = 0, round = 0;

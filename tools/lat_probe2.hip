@@ -12,17 +12,8 @@
 #include <cstdio>
 #include <vector>
 
-#define DEV __device__ __forceinline__
-DEV unsigned U(unsigned v) { return unsigned(__builtin_amdgcn_readfirstlane(int(v))); }
-DEV unsigned wave_scan(unsigned x) {
-    x += unsigned(__builtin_amdgcn_update_dpp(0, int(x), 0x111, 0xF, 0xF, false));
-    x += unsigned(__builtin_amdgcn_update_dpp(0, int(x), 0x112, 0xF, 0xF, false));
-    x += unsigned(__builtin_amdgcn_update_dpp(0, int(x), 0x114, 0xF, 0xF, false));
-    x += unsigned(__builtin_amdgcn_update_dpp(0, int(x), 0x118, 0xF, 0xF, false));
-    x += unsigned(__builtin_amdgcn_update_dpp(0, int(x), 0x142, 0xA, 0xF, false));
-    x += unsigned(__builtin_amdgcn_update_dpp(0, int(x), 0x143, 0xC, 0xF, false));
-    return x;
-}
+#include "../diamond-types_amd/csrc/dt_wave.hpp"
+using namespace dtgpu::wave;
 
 __global__ __launch_bounds__(64) void probe(const unsigned *buf, unsigned *sink, int mode, int hops, unsigned long long *out) {
     __shared__ unsigned s[4096];
@@ -51,7 +42,7 @@ __global__ __launch_bounds__(64) void probe(const unsigned *buf, unsigned *sink,
             idx = U(x);
             break;
         case 4:
-            for (int i = 0; i < hops; i++) x = unsigned(__builtin_amdgcn_readlane(int(wave_scan(x)), 63)) + l;
+            for (int i = 0; i < hops; i++) x = wave_sum(x) + l;
             idx = U(x);
             break;
         case 5:
