@@ -205,26 +205,18 @@ int launch_plan(const PlanParams &q, void *stream, bool walk = true);
 // half, so the walk can run beside the chain decomposition) instead of the entry records
 int launch_walk(const PlanParams &q, void *stream, bool csr);
 
-// One replay pass: the LDS tiers (index in LDS, sized per tier) and then the HBM-index tier,
-// which also replays the LDS-tier documents that outgrew their LDS capacity.  A tier kernel
-// lasts as long as its longest replay, so tiers queued on one stream add up: the biggest tiers
-// (few, long documents) each run on a side stream of their own, forked from and joined back
-// into `stream`, beside the smallest tier; every list indexes docs[].
+// One replay pass: the LDS tiers (index in LDS, sized per tier, smallest index first) and then
+// the HBM-index tier, which also replays the LDS-tier documents that outgrew their LDS capacity.
+// A tier kernel lasts as long as its longest replay, so tiers queued on one stream add up: a pass
+// (dtgpu_pass.cpp) runs the biggest tiers (few, long documents) each on a side stream of its
+// own, beside the smallest tier; every list indexes docs[].
 constexpr int kMaxLdsTiers = 4;
 constexpr int kSideStreams = kMaxLdsTiers - 1;
-struct ReplayLaunch {
-    const BatchParams *lds;   // n_lds LDS tiers, smallest index first
-    int n_lds;
-    const BatchParams *large;
-    void *stream;                   // hipStream_t
-    void *side[kSideStreams];       // hipStream_t: tier n_lds - 1 - k on side[k]
-    void *ev_fork;                  // hipEvent_t
-    void *ev_join[kSideStreams];    // hipEvent_t
-    bool keep_fb = false;           // the fallback counter was reset by the caller (split passes)
-    int join_side = -1;             // split pass: side[join_side] carries the big tier's own
-                                    // prep / plan / replay; s joins it before the HBM tier always
-};
-int launch_replay(const ReplayLaunch &r);
+// One tier's kernel on `stream`, nothing else (no launch for an empty tier); prof: the
+// instrumented kernels (invariant checks, cycle profiles).
+int launch_replay_lds(const BatchParams &q, void *stream, bool prof);
+// The HBM tier: its own list plus a slot per LDS-tier document that may be handed back.
+int launch_replay_hbm(const BatchParams &large, void *stream, bool prof);
 // Transformed-ops replay of large's documents (HBM index tier): BaseMoved positions per LV.
 int launch_replay_xf(const BatchParams &large, void *stream);
 

@@ -1933,7 +1933,8 @@ __global__ __launch_bounds__(COMBINE_THREADS) void combine_kernel(CombineParams 
 
 }  // namespace dev
 
-static int launch_lds_tier(const BatchParams &q, hipStream_t s, bool prof) {
+int launch_replay_lds(const BatchParams &q, void *stream, bool prof) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (!q.n_list) return OK;
     if (q.lds_flat) {   // the flat index: small documents, one wave each
         if (q.lds_blocks > FLAT_MAX_BLOCKS) return ErrArg;
@@ -1981,62 +1982,13 @@ static int launch_lds_tier(const BatchParams &q, hipStream_t s, bool prof) {
     return launch_error() == hipSuccess ? OK : ErrHip;
 }
 
-int launch_replay(const ReplayLaunch &r) {
-    hipStream_t s = reinterpret_cast<hipStream_t>(r.stream);
-    const BatchParams &large = *r.large;
-    bool prof = (large.debug & 3u) != 0;   // invariant checks and cycle profiles: the instrumented kernels
-    uint32_t n_lds = 0;
-    const uint32_t *fb_count = nullptr;
-    for (int t = 0; t < r.n_lds; t++) {
-        prof |= (r.lds[t].debug & 3u) != 0;
-        n_lds += r.lds[t].n_list;
-        if (r.lds[t].fb_count) fb_count = r.lds[t].fb_count;
-    }
-    if (n_lds) {
-        if (fb_count && !r.keep_fb && hipMemsetAsync(const_cast<uint32_t *>(fb_count), 0, sizeof(uint32_t), s) != hipSuccess)
-            return ErrHip;
-        // fork: the biggest tiers start first, each on its own side stream; the smallest tier
-        // runs on the main stream
-        int n_side = 0;
-        while (n_side < kSideStreams && n_side < r.n_lds - 1 && r.side[n_side] && r.ev_join[n_side]) n_side++;
-        const bool fork = n_side > 0 && r.ev_fork;
-        if (fork) {
-            if (hipEventRecord(reinterpret_cast<hipEvent_t>(r.ev_fork), s) != hipSuccess) return ErrHip;
-            for (int k = 0; k < n_side; k++)
-                if (hipStreamWaitEvent(reinterpret_cast<hipStream_t>(r.side[k]), reinterpret_cast<hipEvent_t>(r.ev_fork), 0) !=
-                    hipSuccess)
-                    return ErrHip;
-        }
-        for (int t = r.n_lds - 1; t >= 0; t--) {
-            const int k = r.n_lds - 1 - t;
-            const int e = launch_lds_tier(r.lds[t], (fork && k < n_side) ? reinterpret_cast<hipStream_t>(r.side[k]) : s, prof);
-            if (e) return e;
-        }
-        if (fork) {
-            for (int k = 0; k < n_side; k++)
-                if (hipEventRecord(reinterpret_cast<hipEvent_t>(r.ev_join[k]), reinterpret_cast<hipStream_t>(r.side[k])) != hipSuccess ||
-                    hipStreamWaitEvent(s, reinterpret_cast<hipEvent_t>(r.ev_join[k]), 0) != hipSuccess)
-                    return ErrHip;
-        }
-    }
-    // split pass: the big tier's side pipeline must be done before the HBM tier reads the
-    // fallback queue and before anything synchronising on s sees the batch as finished -- also
-    // when no other LDS tier forked above (then nothing else joined that stream)
-    if (r.join_side >= 0) {
-        if (r.join_side >= kSideStreams || !r.side[r.join_side] || !r.ev_join[r.join_side]) return ErrArg;
-        if (hipEventRecord(reinterpret_cast<hipEvent_t>(r.ev_join[r.join_side]), reinterpret_cast<hipStream_t>(r.side[r.join_side])) !=
-                hipSuccess ||
-            hipStreamWaitEvent(s, reinterpret_cast<hipEvent_t>(r.ev_join[r.join_side]), 0) != hipSuccess)
-            return ErrHip;
-    }
-    // HBM tier: its own list plus a slot per LDS-tier document that may be handed back
+int launch_replay_hbm(const BatchParams &large, void *stream, bool prof) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const uint32_t grid = large.n_list + (large.fb_list ? large.fb_slots : 0);
-    if (grid) {
-        if (prof) hipLaunchKernelGGL((dev::replay_kernel<dev::IX_HBM, true, false>), dim3(grid), dim3(64), 0, s, large);
-        else hipLaunchKernelGGL((dev::replay_kernel<dev::IX_HBM, false, false>), dim3(grid), dim3(64), 0, s, large);
-        if (launch_error() != hipSuccess) return ErrHip;
-    }
-    return OK;
+    if (!grid) return OK;
+    if (prof) hipLaunchKernelGGL((dev::replay_kernel<dev::IX_HBM, true, false>), dim3(grid), dim3(64), 0, s, large);
+    else hipLaunchKernelGGL((dev::replay_kernel<dev::IX_HBM, false, false>), dim3(grid), dim3(64), 0, s, large);
+    return launch_error() == hipSuccess ? OK : ErrHip;
 }
 
 // Transformed-ops replay (iter_xf_operations): HBM-tier index, one workgroup per document of

@@ -9,104 +9,17 @@ using namespace dtgpu;
 
 namespace {
 
-int replay_all(dtgpu_batch *B, hipStream_t s, int skip_tier = -1) {
-    ReplayLaunch r{};
-    BatchParams tiers[kLdsTiers];
-    for (int t = 0; t < kLdsTiers; t++) {
-        tiers[t] = B->tier[t];
-        if (t == skip_tier) tiers[t].n_list = 0;   // replayed by the split pipeline
-    }
-    r.lds = tiers;
-    r.keep_fb = skip_tier >= 0;
-    r.join_side = skip_tier >= 0 ? kLdsTiers - 1 - skip_tier : -1;   // launch_split_side's stream
-    r.n_lds = kLdsTiers;
-    r.large = &B->large;
-    r.stream = s;
-    for (int k = 0; k < kSideStreams; k++) { r.side[k] = B->side[k]; r.ev_join[k] = B->ev_join[k]; }
-    r.ev_fork = B->ev_fork;
-    // split pass: a segment of a big-tier document may sit in a tier replayed from s
-    if (skip_tier >= 0 && !B->seg_groups.empty() && hipStreamWaitEvent(s, B->ev_splan, 0) != hipSuccess) return ErrHip;
-    const int e = launch_replay(r);
-    return e ? e : launch_combine(B->comb, s);   // cut documents: their segments' texts joined
-}
-// A split pass plans its cuts beside the side pipeline's prep, before the main pipeline's: the cut
-// kernel then finds each parent's entry itself.
-CutParams cut_before_prep(const dtgpu_batch *B) {
-    CutParams c = B->cut;
-    c.pent = nullptr;
-    return c;
-}
-// The split pass's side pipeline (see stage_device): after a fork from s, the big tier's
-// prep, plan and replay on its side stream.  The fallback counter is reset first, on s, since
-// both pipelines' LDS tiers append to it; the main pipeline's replay_all(skip_tier) joins the
-// side stream (launch_replay's fork / join of that tier's stream) before the HBM tier.
-int launch_split_side(dtgpu_batch *B, hipStream_t s) {
-    const int tb = B->split_tier;
-    hipStream_t sb = B->side[kLdsTiers - 1 - tb];
-    const BatchParams &q = B->tier[tb];
-    if (q.fb_count && hipMemsetAsync(const_cast<uint32_t *>(q.fb_count), 0, sizeof(uint32_t), s) != hipSuccess) return ErrHip;
-    if (hipEventRecord(B->ev_fork, s) != hipSuccess || hipStreamWaitEvent(sb, B->ev_fork, 0) != hipSuccess) return ErrHip;
-    PrepParams pp = B->prep;
-    pp.doc_list = B->d_split.p;
-    pp.n_docs = B->n_big;
-    PlanParams qq = B->plan;
-    qq.doc_list = B->d_split.p;
-    qq.n_docs = B->n_big;
-    // as prep_and_plan: the walk (CSR mode, after prep's first half) on a stream of its own,
-    // beside the chain decomposition and prep's second half
-    const bool overlap = B->n_gpu_planned && B->prep.chain_flag && !B->prep.check && B->plan.walk && B->plan.coff &&
-                         B->ws_side && B->cfg.walk_overlap;
-    if (overlap) {
-        pp.short_rec = B->plan.split ? 1u : 0u;
-        if (launch_prep_stage(pp, sb, 1)) return ErrHip;
-        if (hipEventRecord(B->ev_sw0, sb) != hipSuccess || hipStreamWaitEvent(B->ws_side, B->ev_sw0, 0) != hipSuccess) return ErrHip;
-        if (launch_walk(qq, B->ws_side, true) != OK || hipEventRecord(B->ev_sw1, B->ws_side) != hipSuccess) return ErrHip;
-        if (launch_prep_stage(pp, sb, 2) || launch_prep_stage(pp, sb, 3)) return ErrHip;
-        if (hipStreamWaitEvent(sb, B->ev_sw1, 0) != hipSuccess || launch_plan(qq, sb, false) != OK) return ErrHip;
-    } else {
-        if (launch_prep(pp, sb)) return ErrHip;
-        if (B->n_gpu_planned && launch_plan(qq, sb) != OK) return ErrHip;
-    }
-    if (hipEventRecord(B->ev_splan, sb) != hipSuccess) return ErrHip;
-    // the cut planning on s, beside the side pipeline's prep and plan (the main pipeline's prep
-    // follows it there); the side replay waits for it
-    if (B->cut.n_groups && (launch_cut(cut_before_prep(B), s) || hipEventRecord(B->ev_cut, s) != hipSuccess ||
-                            hipStreamWaitEvent(sb, B->ev_cut, 0) != hipSuccess))
-        return ErrHip;
-    BatchParams tiers[kLdsTiers];
-    for (int t = 0; t < kLdsTiers; t++) {
-        tiers[t] = B->tier[t];
-        if (t != tb) tiers[t].n_list = 0;
-    }
-    BatchParams large = B->large;
-    large.n_list = 0;
-    large.fb_slots = 0;
-    ReplayLaunch r{};
-    r.lds = tiers;
-    r.n_lds = kLdsTiers;
-    r.large = &large;
-    r.stream = sb;
-    r.keep_fb = true;
-    return launch_replay(r);
-}
-// The main pipeline's prep and plan of a split pass (the documents outside the big tier).
-int launch_split_prep(dtgpu_batch *B, hipStream_t s) {
-    PrepParams pp = B->prep;
-    pp.doc_list = B->d_split.p + B->n_big;
-    pp.n_docs = B->n_rest;
-    return launch_prep(pp, s) ? ErrHip : OK;
-}
-int launch_split_plan(dtgpu_batch *B, hipStream_t s) {
-    if (!B->n_gpu_planned) return OK;
-    PlanParams qq = B->plan;
-    qq.doc_list = B->d_split.p + B->n_big;
-    qq.n_docs = B->n_rest;
-    return launch_plan(qq, s);
+// Every record / wait between a pass's streams is in this file (DESIGN.md §5e draws each pass
+// shape); the launch_* functions only put a kernel on the stream they are given.
+int wait_for(hipStream_t s, hipEvent_t e) { return hipStreamWaitEvent(s, e, 0) == hipSuccess ? OK : ErrHip; }
+// `to` waits, through e, for what `from` holds so far.
+int hop(hipEvent_t e, hipStream_t from, hipStream_t to) {
+    return hipEventRecord(e, from) == hipSuccess ? wait_for(to, e) : ErrHip;
 }
 
 // Prep then plan for a device-staged batch, as one pipeline: its documents (doc_list / n_docs of
 // prep and plan), its cut groups, its stream, its walk stream and the events between the two (w0:
-// prep's first half is done).  A whole pass has one pipeline over B's own parameters, a
+// prep's first half is done).  A whole pass has one pipeline over B's own parameters, a split or
 // late-pipeline pass two.  With the three-launch prep and the walk kernel, the walk (CSR mode: it
 // needs only prep's first half) runs on the walk stream beside the chain decomposition and prep's
 // second half, and the plan kernel waits for it; the pipeline's cut planning (if it has cut groups)
@@ -120,6 +33,17 @@ struct Pipe {
 };
 Pipe whole_pipe(const dtgpu_batch *B, hipStream_t s) {
     return Pipe{B->prep, B->plan, B->cut, s, B->wstream, B->ev_w0, B->ev_w1, B->ev_cut};
+}
+// One of a pass's two pipelines: n documents of `list` on s, the walk on w.  It plans no cuts:
+// the pass does, once for both.
+Pipe list_pipe(const dtgpu_batch *B, hipStream_t s, const uint32_t *list, uint32_t n, hipStream_t w, hipEvent_t w0,
+               hipEvent_t w1) {
+    Pipe p = whole_pipe(B, s);
+    p.prep.doc_list = p.plan.doc_list = list;
+    p.prep.n_docs = p.plan.n_docs = n;
+    p.cut.n_groups = 0;
+    p.w = w; p.w0 = w0; p.w1 = w1; p.cut_done = nullptr;
+    return p;
 }
 bool walk_beside(const dtgpu_batch *B, const Pipe &p) {
     return B->dec && B->n_gpu_planned && p.prep.chain_flag && !p.prep.check && p.plan.walk && p.plan.coff && p.w &&
@@ -137,8 +61,7 @@ int pipe_prep(dtgpu_batch *B, const Pipe &p, hipEvent_t mid) {
     // the walk reads prep's CSR and, split, the planner only the entry records' heads
     PrepParams pp = p.prep;
     pp.short_rec = p.plan.split ? 1u : 0u;
-    if (launch_prep_stage(pp, s, 1)) return ErrHip;
-    if (hipEventRecord(p.w0, s) != hipSuccess || hipStreamWaitEvent(p.w, p.w0, 0) != hipSuccess) return ErrHip;
+    if (launch_prep_stage(pp, s, 1) || hop(p.w0, s, p.w)) return ErrHip;
     if (launch_walk(p.plan, p.w, true) != OK) return ErrHip;
     if (hipEventRecord(p.w1, p.w) != hipSuccess) return ErrHip;
     // the cut planning after the walk (it reads prep's parent entries), beside prep's second half
@@ -152,14 +75,89 @@ int pipe_prep(dtgpu_batch *B, const Pipe &p, hipEvent_t mid) {
 int pipe_plan(dtgpu_batch *B, const Pipe &p) {
     hipStream_t s = p.s;
     const bool beside = walk_beside(B, p);
-    if (beside && hipStreamWaitEvent(s, p.w1, 0) != hipSuccess) return ErrHip;
+    if (beside && wait_for(s, p.w1)) return ErrHip;
     if (B->n_gpu_planned && launch_plan(p.plan, s, !beside) != OK) return ErrHip;
-    if (beside && p.cut.n_groups && hipStreamWaitEvent(s, p.cut_done, 0) != hipSuccess) return ErrHip;
+    if (beside && p.cut.n_groups && wait_for(s, p.cut_done)) return ErrHip;
     return OK;
 }
 int prep_and_plan(dtgpu_batch *B, const Pipe &p, hipEvent_t mid) {
     const int e = pipe_prep(B, p, mid);
     return e ? e : pipe_plan(B, p);
+}
+
+// The instrumented replay kernels (invariant checks, cycle profiles): B->debug is the debug word
+// of every tier and of the HBM tier (set_tier_params).
+bool instrumented(const dtgpu_batch *B) { return (B->debug & 3u) != 0; }
+// LDS tier t >= 1 replays on a side stream of its own, the biggest tier on side[0].
+int side_of(int t) { return kLdsTiers - 1 - t; }
+// The hand-back counter to zero, on s: one for the batch, every LDS tier appends to it.
+int reset_handback(dtgpu_batch *B, hipStream_t s) {
+    uint32_t *n = const_cast<uint32_t *>(B->tier[0].fb_count);
+    return !n || hipMemsetAsync(n, 0, sizeof(uint32_t), s) == hipSuccess ? OK : ErrHip;
+}
+// The tail of every tracker pass on s: the HBM tier (its own documents and whatever the LDS tiers
+// handed back), then the cut documents' texts joined from their segments'.
+int replay_hbm_and_combine(dtgpu_batch *B, hipStream_t s) {
+    const int e = launch_replay_hbm(B->large, s, instrumented(B));
+    return e ? e : launch_combine(B->comb, s);
+}
+// The replay of a whole pass, or the main pipeline's of a split pass (skip_tier: replayed by the
+// side pipeline, which reset the counter).  If an LDS tier has documents: fork from s to every
+// side stream, the biggest tiers first, each on its side stream, the smallest on s, and every
+// side stream joined back into s -- the split tier's too, with the side pipeline on it.
+int replay_all(dtgpu_batch *B, hipStream_t s, int skip_tier = -1) {
+    const bool split = skip_tier >= 0;
+    // split pass: a segment of a big-tier document may sit in a tier replayed from s
+    if (split && !B->seg_groups.empty() && wait_for(s, B->ev_splan)) return ErrHip;
+    uint32_t n_lds = 0;
+    for (int t = 0; t < kLdsTiers; t++) n_lds += t != skip_tier ? B->tier[t].n_list : 0;
+    if (n_lds) {
+        if (!split && reset_handback(B, s)) return ErrHip;
+        if (hipEventRecord(B->ev_fork, s) != hipSuccess) return ErrHip;
+        for (int k = 0; k < kSideStreams; k++)
+            if (wait_for(B->side[k], B->ev_fork)) return ErrHip;
+        for (int t = kLdsTiers - 1; t >= 0; t--) {
+            if (t == skip_tier) continue;
+            if (const int e = launch_replay_lds(B->tier[t], t ? B->side[side_of(t)] : s, instrumented(B))) return e;
+        }
+        for (int k = 0; k < kSideStreams; k++)
+            if (hop(B->ev_join[k], B->side[k], s)) return ErrHip;
+    } else if (split) {
+        // nothing forked, so nothing else joins the side pipeline: it must be done before the
+        // HBM tier reads the hand-back queue and before anything synchronising on s sees the
+        // batch as finished
+        const int k = side_of(skip_tier);
+        if (hop(B->ev_join[k], B->side[k], s)) return ErrHip;
+    }
+    return replay_hbm_and_combine(B, s);
+}
+
+// A split pass plans its cuts beside the side pipeline's prep, before the main pipeline's: the cut
+// kernel then finds each parent's entry itself.
+CutParams cut_before_prep(const dtgpu_batch *B) {
+    CutParams c = B->cut;
+    c.pent = nullptr;
+    return c;
+}
+// The split pass's side pipeline (see stage_device): after a fork from s, the big tier's prep,
+// plan and replay on its side stream.  The hand-back counter is reset first, on s, since both
+// pipelines' LDS tiers append to it; the main pipeline's replay_all(skip_tier) joins the side
+// stream before the HBM tier.
+int launch_split_side(dtgpu_batch *B, hipStream_t s) {
+    hipStream_t sb = B->side[side_of(B->split_tier)];
+    if (reset_handback(B, s) || hop(B->ev_fork, s, sb)) return ErrHip;
+    Pipe p = list_pipe(B, sb, B->d_split.p, B->n_big, B->ws_side, B->ev_sw0, B->ev_sw1);
+    if (!walk_beside(B, p)) p.w0 = nullptr;   // (no walk stream in use: nothing waits for prep's first half)
+    if (const int e = prep_and_plan(B, p, nullptr)) return e;
+    if (hipEventRecord(B->ev_splan, sb) != hipSuccess) return ErrHip;
+    // the cut planning on s, beside the side pipeline's prep and plan (the main pipeline's prep
+    // follows it there); the side replay waits for it
+    if (B->cut.n_groups && (launch_cut(cut_before_prep(B), s) || hop(B->ev_cut, s, sb))) return ErrHip;
+    return launch_replay_lds(B->tier[B->split_tier], sb, instrumented(B));
+}
+// The main pipeline of a split pass: the documents outside the big tier, all on s.
+Pipe split_main_pipe(const dtgpu_batch *B, hipStream_t s) {
+    return list_pipe(B, s, B->d_split.p + B->n_big, B->n_rest, nullptr, nullptr, nullptr);
 }
 
 // The linear documents' checkout (dt_ff.hip) on s: first in a pass, or, in a split pass, right
@@ -173,23 +171,13 @@ bool tracker_pass(const dtgpu_batch *B) { return B->n_track != 0 || B->ff_doc.em
 struct PassMarks { hipEvent_t start = nullptr, prepped = nullptr, planned = nullptr; };
 int mark(hipEvent_t e, hipStream_t s) { return !e || hipEventRecord(e, s) == hipSuccess ? OK : ErrHip; }
 
-// A replay launch of `count` workgroups of the flat tier's list from `first` on, nothing else.
+// `count` workgroups of the flat tier's list from `first` on, on s.
 int replay_flat_range(dtgpu_batch *B, hipStream_t s, uint32_t first, uint32_t count, bool all_late) {
-    BatchParams tiers[kLdsTiers];
-    for (int t = 0; t < kLdsTiers; t++) { tiers[t] = B->tier[t]; tiers[t].n_list = 0; }
-    tiers[0].doc_list = B->tier[0].doc_list + first;
-    tiers[0].n_list = count;
-    tiers[0].all_late = all_late ? 1u : 0u;
-    BatchParams large = B->large;
-    large.n_list = 0;
-    large.fb_slots = 0;
-    ReplayLaunch r{};   // (no side streams: one tier)
-    r.lds = tiers;
-    r.n_lds = kLdsTiers;
-    r.large = &large;
-    r.stream = s;
-    r.keep_fb = true;
-    return launch_replay(r);
+    BatchParams q = B->tier[0];
+    q.doc_list += first;
+    q.n_list = count;
+    q.all_late = all_late ? 1u : 0u;
+    return launch_replay_lds(q, s, instrumented(B));
 }
 // A pass with the late pipeline (dt_batch.hpp late_pipe).  On s: prep and plan of the first
 // round's documents, then their replay.  On side[0] (the walk on side[1]), from the end of the
@@ -204,53 +192,32 @@ int replay_flat_range(dtgpu_batch *B, hipStream_t s, uint32_t first, uint32_t co
 // after the first round's replay is launched -- it and the late replay, every workgroup at the
 // raised priority, then queue for the slots the first round frees.  s joins side[0] before the
 // HBM tier (its own documents and whatever either launch handed back) and the combine step.
-// The marks are the main pipeline's, as in a split pass.
+// The hand-back counter is reset once, at the start.  The marks are the main pipeline's, as in
+// a split pass.
 int launch_late_pass(dtgpu_batch *B, hipStream_t s, const PassMarks &m) {
-    hipStream_t sl = B->side[0];
-    const BatchParams &q = B->tier[0];
-    if (q.fb_count && hipMemsetAsync(const_cast<uint32_t *>(q.fb_count), 0, sizeof(uint32_t), s) != hipSuccess) return ErrHip;
-    Pipe a = whole_pipe(B, s);
-    a.prep.doc_list = a.plan.doc_list = B->d_late.p;
-    a.prep.n_docs = a.plan.n_docs = B->n_first;
-    a.cut.n_groups = 0;   // (below, for both pipelines)
-    Pipe b = whole_pipe(B, sl);
-    b.prep.doc_list = b.plan.doc_list = B->d_late.p + B->n_first;
-    b.prep.n_docs = b.plan.n_docs = B->n_late;
-    b.cut.n_groups = 0;
-    b.w = B->side[1]; b.w0 = B->ev_sw0; b.w1 = B->ev_sw1; b.cut_done = nullptr;
+    hipStream_t sl = B->side[0], w = B->wstream;
+    if (reset_handback(B, s)) return ErrHip;
+    const Pipe a = list_pipe(B, s, B->d_late.p, B->n_first, w, B->ev_w0, B->ev_w1);
+    const Pipe b = list_pipe(B, sl, B->d_late.p + B->n_first, B->n_late, B->side[1], B->ev_sw0, B->ev_sw1);
     int e = pipe_prep(B, a, m.prepped);
     if (e) return e;
-    if (hipStreamWaitEvent(sl, B->ev_w0, 0) != hipSuccess || (e = pipe_prep(B, b, nullptr))) return e ? e : ErrHip;
-    if (walk_beside(B, b) && hipStreamWaitEvent(sl, b.w1, 0) != hipSuccess) return ErrHip;
+    if (wait_for(sl, B->ev_w0) || (e = pipe_prep(B, b, nullptr))) return e ? e : ErrHip;
+    if (walk_beside(B, b) && wait_for(sl, b.w1)) return ErrHip;
     if (hipEventRecord(B->ev_lprep, sl) != hipSuccess) return ErrHip;
     if (B->cut.n_groups) {   // (it reads both first halves' parent entries)
-        hipStream_t w = B->wstream;
-        if (hipStreamWaitEvent(w, B->ev_w0, 0) != hipSuccess || hipStreamWaitEvent(w, B->ev_sw0, 0) != hipSuccess ||
-            launch_cut(B->cut, w) || hipEventRecord(B->ev_cut, w) != hipSuccess)
+        if (wait_for(w, B->ev_w0) || wait_for(w, B->ev_sw0) || launch_cut(B->cut, w) || hipEventRecord(B->ev_cut, w) != hipSuccess)
             return ErrHip;
     }
     if ((e = pipe_plan(B, a)) || (e = mark(m.planned, s))) return e;
-    if (hipStreamWaitEvent(s, B->ev_lprep, 0) != hipSuccess || (B->cut.n_groups && hipStreamWaitEvent(s, B->ev_cut, 0) != hipSuccess) ||
-        hipEventRecord(B->ev_fork, s) != hipSuccess)
-        return ErrHip;
+    if (wait_for(s, B->ev_lprep) || (B->cut.n_groups && wait_for(s, B->ev_cut))) return ErrHip;
+    // (ev_fork: the first round's replay is launched)
+    if (hipEventRecord(B->ev_fork, s) != hipSuccess) return ErrHip;
     if ((e = replay_flat_range(B, s, 0, B->flat_first, false))) return e;
-    if (hipStreamWaitEvent(B->wstream, B->ev_fork, 0) != hipSuccess || hipEventRecord(B->ev_lgo, B->wstream) != hipSuccess ||
-        hipStreamWaitEvent(sl, B->ev_lgo, 0) != hipSuccess)
-        return ErrHip;
+    if (wait_for(w, B->ev_fork) || hop(B->ev_lgo, w, sl)) return ErrHip;
     if ((e = pipe_plan(B, b))) return e;
-    if ((e = replay_flat_range(B, sl, B->flat_first, q.n_list - B->flat_first, true))) return e;
-    if (hipEventRecord(B->ev_join[0], sl) != hipSuccess || hipStreamWaitEvent(s, B->ev_join[0], 0) != hipSuccess) return ErrHip;
-    // the HBM tier and the combine step, as replay_all's
-    BatchParams none[kLdsTiers];
-    for (int t = 0; t < kLdsTiers; t++) { none[t] = B->tier[t]; none[t].n_list = 0; }
-    ReplayLaunch r{};
-    r.lds = none;
-    r.n_lds = kLdsTiers;
-    r.large = &B->large;
-    r.stream = s;
-    r.keep_fb = true;
-    e = launch_replay(r);
-    return e ? e : launch_combine(B->comb, s);
+    if ((e = replay_flat_range(B, sl, B->flat_first, B->tier[0].n_list - B->flat_first, true))) return e;
+    if (hop(B->ev_join[0], sl, s)) return ErrHip;
+    return replay_hbm_and_combine(B, s);
 }
 // The tracker part of a pass on s, after the fast-forward pass: prep (device-staged: the walker
 // inputs first), plan, replay -- every entry point's, timed or not.
@@ -280,8 +247,7 @@ int launch_pass(dtgpu_batch *B, hipStream_t s, const PassMarks &m = {}) {
     if (e || !track) return e;
     if (!B->split) return launch_tracker(B, s, m);
     // prep / plan times are the main pipeline's
-    if ((e = launch_split_prep(B, s)) || (e = mark(m.prepped, s)) || (e = launch_split_plan(B, s))) return e;
-    if (mark(m.planned, s)) return ErrHip;
+    if ((e = prep_and_plan(B, split_main_pipe(B, s), m.prepped)) || (e = mark(m.planned, s))) return e;
     return replay_all(B, s, B->split_tier);
 }
 
@@ -312,7 +278,8 @@ dtgpu_status dtgpu_batch_run_e2e_timed(dtgpu_batch *B, float ms[4]) {
     if (launch_decode(B->dec->P, s)) return DTGPU_ERR_HIP;
     if (hipEventRecord(B->ev_prep, s) != hipSuccess) return DTGPU_ERR_HIP;
     if (launch_ff_pass(B, s)) return DTGPU_ERR_HIP;   // linear documents (dt_ff.hip)
-    // (the same tracker pass as dtgpu_batch_run's, its marks between prep, plan and replay)
+    // (the same tracker pass as dtgpu_batch_run's, its marks between prep, plan and replay; not
+    // through launch_pass: no pass mark, and a split-eligible batch runs as one whole pipeline)
     const int st = tracker_pass(B) ? launch_tracker(B, s, PassMarks{nullptr, B->ev0, B->ev_mid})
                                    : (mark(B->ev0, s) || mark(B->ev_mid, s) ? ErrHip : OK);
     if (st) return dtgpu_status(st);

@@ -97,14 +97,19 @@ def test_split_pass_joins_big_tier(case):
         docs = [G.dt_bytes("node_nodecc"), b"nope"]
     else:
         docs = [G.dt_bytes("git-makefile"), _hbm_tier_doc()]
-    for timed in (False, True):
+    # run_e2e_timed() takes no split pass: the same batch as one whole pipeline, same texts
+    modes = ("run", "timed") + (("e2e",) if case == "big_tier_with_hbm_doc" else ())
+    for mode in modes:
         b = dt_amd.Batch(docs=docs, staging="device")
-        if timed:
-            b.run_timed()
+        if mode == "run":
+            res, texts = _texts(b)
+        else:
+            if mode == "timed":
+                b.run_timed()
+            else:
+                assert len(b.run_e2e_timed()) == 4
             res = b.results()
             texts = [b.text(i) if r["status"] == 0 else None for i, r in enumerate(res)]
-        else:
-            res, texts = _texts(b)
         assert res[0]["status"] == 0
         want = OracleOpLog.load_from(docs[0]).checkout_tip_bytes()
         assert hashlib.sha256(texts[0]).hexdigest() == hashlib.sha256(want).hexdigest()
