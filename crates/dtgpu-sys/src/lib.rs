@@ -18,6 +18,10 @@ pub struct dtgpu_decoded {
     _p: [u8; 0],
 }
 #[repr(C)]
+pub struct dtgpu_patches {
+    _p: [u8; 0],
+}
+#[repr(C)]
 #[derive(Default, Clone, Copy, Debug)]
 pub struct dtgpu_doc_result {
     pub status: u32,
@@ -124,6 +128,17 @@ extern "C" {
                                 out: *mut *mut dtgpu_decoded) -> dtgpu_status;
     pub fn dtgpu_decode_history_result(hist: *const dtgpu_decoded, i: usize, frontier: *mut u64, cap: usize,
                                        n_frontier: *mut usize) -> dtgpu_status;
+    // ListOpLog::encode_from(opts, from) for a batch (encode_oplog.rs:404-747)
+    pub fn dtgpu_decode_encode_from(base: *const dtgpu_decoded, doc: *const u32, versions: *const u64,
+                                    version_off: *const usize, n: usize, flags: u32, ms: *mut f32,
+                                    out: *mut *mut dtgpu_patches) -> dtgpu_status;
+    pub fn dtgpu_patches_size(p: *const dtgpu_patches) -> usize;
+    pub fn dtgpu_patches_result(p: *const dtgpu_patches, i: usize, frontier: *mut u64, cap: usize,
+                                n_frontier: *mut usize) -> dtgpu_status;
+    pub fn dtgpu_patches_get(p: *const dtgpu_patches, i: usize, out: *mut u8, cap: usize,
+                             out_len: *mut usize) -> dtgpu_status;
+    pub fn dtgpu_patches_profile(p: *const dtgpu_patches, i: usize, out: *mut u32) -> dtgpu_status;
+    pub fn dtgpu_patches_free(p: *mut dtgpu_patches);
     pub fn dtgpu_batch_create_decoded(dec: *mut dtgpu_decoded, out: *mut *mut dtgpu_batch) -> dtgpu_status;
     pub fn dtgpu_device_count() -> c_int;
     // the decoded oplog's arrays (op runs, inserted content, per-LV byte offsets, ...)

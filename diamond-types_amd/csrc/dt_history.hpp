@@ -27,7 +27,7 @@ struct HistDesc {
     uint32_t b_complete, skip;   // skip: the status to report without projecting (0: project)
     // the request: LVs of the base document in HistParams::req
     uint64_t req_off;
-    uint32_t n_req, use_lds;     // use_lds: the mark words live in LDS during the sweep
+    uint32_t n_req, use_lds;     // use_lds: the mark words live in LDS during the sweep (2: and it fences at agent scope)
     uint64_t scr_off;            // HIST_ENT_WORDS * b_n_ent words of HistParams::scr
     // output arenas (emit launch): offsets in elements and capacities
     uint64_t o_in, o_arun, o_op, o_ent, o_poff, o_par, o_content, o_lv, o_agent, o_ver;

@@ -19,8 +19,22 @@
 #include "dt_decoded.hpp"
 #include "dt_history.hpp"
 #include "dt_host.hpp"
+#include "dt_patch.hpp"
 
 using namespace dtgpu;
+
+// dtgpu_decode_encode_from's result: the patches in one HBM arena (owned), each request's reduced
+// frontier, status and length
+struct dtgpu_patches {
+    int device = 0;
+    size_t n = 0;
+    float mark_ms = 0, build_ms = 0;
+    std::vector<PatchResult> res;
+    std::vector<uint32_t> n_front, form;
+    std::vector<uint64_t> out_off;
+    DevBuf<uint32_t> front;
+    DevBuf<uint8_t> out;
+};
 
 namespace {
 
@@ -537,6 +551,7 @@ dtgpu_status dtgpu_decode_history(const dtgpu_decoded *B, const uint32_t *doc, c
     // the mark words of an output live in LDS up to this many base entries, in its HBM scratch
     // past it (DTGPU_HISTORY_LDS_ENTRIES lowers the limit; 0: always HBM)
     uint32_t lds_cap = HIST_LDS_ENTRIES;
+    const uint32_t lds_form = getenv("DTGPU_MARK_AGENT_FENCE") ? 2u : 1u;   // (measurement: the sweep's earlier fence)
     if (const char *e = getenv("DTGPU_HISTORY_LDS_ENTRIES")) lds_cap = uint32_t(std::min<unsigned long>(strtoul(e, nullptr, 10), HIST_LDS_ENTRIES));
     std::vector<HistDesc> hd(n, HistDesc{});
     std::vector<uint32_t> req(n_req);
@@ -558,7 +573,7 @@ dtgpu_status dtgpu_decode_history(const dtgpu_decoded *B, const uint32_t *doc, c
         h.n_req = uint32_t(version_off[i + 1] - version_off[i]);
         for (size_t k = version_off[i]; k < version_off[i + 1]; k++)
             req[k - version_off[0]] = uint32_t(std::min<uint64_t>(versions[k], 0xFFFFFFFFull));
-        h.use_lds = h.b_n_ent <= lds_cap ? 1u : 0u;
+        h.use_lds = h.b_n_ent <= lds_cap ? lds_form : 0u;
         if (h.use_lds && !h.skip) lds_entries = std::max(lds_entries, h.b_n_ent);
         h.scr_off = scr;
         scr += uint64_t(HIST_ENT_WORDS) * h.b_n_ent;
@@ -653,6 +668,196 @@ dtgpu_status dtgpu_decode_history_result(const dtgpu_decoded *H, size_t i, uint6
     }
     return dtgpu_status(st);
 }
+
+// ListOpLog::encode_from(opts, from) for a batch (dt_patch.hip).  Staging as dtgpu_decode_history:
+// the request CSR goes to HBM, the mark launch reduces every request and counts its patch, each
+// request's scratch and output are laid out from those counts (patch_words / patch_bytes and the
+// byte bound below), and the build launch writes the files.
+dtgpu_status dtgpu_decode_encode_from(const dtgpu_decoded *B, const uint32_t *doc, const uint64_t *versions,
+                                      const size_t *version_off, size_t n, uint32_t flags, float *ms,
+                                      dtgpu_patches **out) {
+    if (out) *out = nullptr;
+    if (!B || !out || (n && (!doc || !version_off))) return DTGPU_ERR_ARG;
+    if (!B->merged && !B->ran) return DTGPU_ERR_ARG;   // not decoded yet
+    if (flags & ~uint32_t(DTGPU_ENCODE_FULL)) return DTGPU_ERR_ARG;
+    for (size_t i = 0; i < n; i++)
+        if (doc[i] >= B->n || version_off[i + 1] < version_off[i]) return DTGPU_ERR_ARG;
+    const size_t n_req = n ? version_off[n] - version_off[0] : 0;
+    if (n_req && !versions) return DTGPU_ERR_ARG;
+    auto M = new dtgpu_patches();
+    std::unique_ptr<dtgpu_patches> guard(M);
+    M->device = B->device;
+    M->n = n;
+#define CK(x) do { if (DTGPU_HIP_FAILED(x)) return DTGPU_ERR_HIP; } while (0)
+    CK(hipSetDevice(M->device));
+    struct Own {
+        hipStream_t s = nullptr;
+        hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+        ~Own() {
+            for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x);
+            if (s) (void)hipStreamDestroy(s);
+        }
+    } own;
+    CK(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking));
+    for (hipEvent_t &e : own.e) CK(hipEventCreate(&e));
+    hipStream_t s = own.s;
+    std::vector<HistDesc> hd(n, HistDesc{});
+    std::vector<uint32_t> req(n_req);
+    uint64_t scr = 0;
+    // the mark sweep's words: in LDS or in HBM scratch, by the history projection's rule and override
+    uint32_t lds_cap = HIST_LDS_ENTRIES, lds_entries = 0;
+    const uint32_t lds_form = getenv("DTGPU_MARK_AGENT_FENCE") ? 2u : 1u;   // (measurement: the sweep's earlier fence)
+    if (const char *e = getenv("DTGPU_HISTORY_LDS_ENTRIES")) lds_cap = uint32_t(std::min<unsigned long>(strtoul(e, nullptr, 10), HIST_LDS_ENTRIES));
+    for (size_t i = 0; i < n; i++) {
+        const DecodeDesc &bd = B->desc[doc[i]];
+        const DecodeResult &br = B->res[doc[i]];
+        HistDesc &h = hd[i];
+        h.skip = br.status;
+        h.b_in = bd.in_off; h.b_arun = bd.arun_off; h.b_op = bd.op_off; h.b_ent = bd.ent_off; h.b_poff = bd.poff_off;
+        h.b_par = bd.par_off; h.b_content = bd.content_off; h.b_lv = bd.lv_off; h.b_agent = bd.agent_off;
+        if (br.status == 0) {
+            h.b_in_len = bd.in_len; h.b_n_aruns = br.n_aruns; h.b_n_ops = br.n_ops; h.b_n_ent = br.n_entries;
+            h.b_n_par = br.n_parents; h.b_n_content = br.n_content; h.b_n_agents = br.n_agents;
+            h.b_n_lv = uint32_t(std::min<uint64_t>(br.n_lv, 0xFFFFFFFFull)); h.b_complete = br.content_complete;
+        }
+        h.req_off = version_off[i] - version_off[0];
+        h.n_req = uint32_t(version_off[i + 1] - version_off[i]);
+        for (size_t k = version_off[i]; k < version_off[i + 1]; k++)
+            req[k - version_off[0]] = uint32_t(std::min<uint64_t>(versions[k], 0xFFFFFFFFull));
+        h.use_lds = h.b_n_ent <= lds_cap ? lds_form : 0u;
+        if (h.use_lds && !h.skip) lds_entries = std::max(lds_entries, h.b_n_ent);
+        h.scr_off = scr;
+        scr += uint64_t(HIST_ENT_WORDS) * h.b_n_ent;
+        h.o_ver = uint64_t(DECODE_MAX_FRONTIER) * i;
+    }
+    DevBuf<uint32_t> d_req, d_scr, d_ver, d_w;
+    DevBuf<uint8_t> d_b;
+    DevBuf<HistDesc> d_hd;
+    DevBuf<PatchDesc> d_pd;
+    DevBuf<PatchCounts> d_cnt;
+    DevBuf<PatchResult> d_res;
+    CK(d_req.upload(req, s));
+    CK(d_scr.alloc(scr));
+    CK(d_hd.upload(hd, s));
+    CK(d_ver.alloc(uint64_t(DECODE_MAX_FRONTIER) * n));
+    CK(M->front.alloc(uint64_t(DECODE_MAX_FRONTIER) * n));
+    CK(d_cnt.alloc(n));
+    CK(d_res.alloc(n));
+    PatchParams P{};
+    HistParams &H = P.H;
+    H.b_in = B->in.p; H.b_content = B->content.p; H.b_aruns = B->aruns.p; H.b_ops = B->ops.p; H.b_ent = B->ent.p;
+    H.b_poff = B->poff.p; H.b_par = B->par.p; H.b_cbyte = B->cbyte.p; H.b_agents = B->agents.p;
+    H.req = d_req.p; H.scr = d_scr.p; H.o_ver = d_ver.p; H.o_front = M->front.p;
+    H.docs = d_hd.p; H.n_docs = uint32_t(n);
+    P.counts = d_cnt.p; P.results = d_res.p; P.n_docs = uint32_t(n); P.lds_entries = lds_entries;
+    P.prof = getenv("DTGPU_PATCH_PROF") ? 1u : 0u;   // read at call time: the build waves count their phase cycles
+    P.flags = flags & (DTGPU_ENCODE_STORE_INSERTED_CONTENT | DTGPU_ENCODE_COMPRESS_CONTENT);
+    P.x2n[0] = 1u << 30;
+    for (int k = 1; k < 32; k++) P.x2n[k] = multmodp_host(P.x2n[k - 1], P.x2n[k - 1]);
+    CK(hipEventRecord(own.e[0], s));
+    if (launch_patch_mark(P, s)) return DTGPU_ERR_HIP;
+    CK(hipEventRecord(own.e[1], s));
+    std::vector<PatchCounts> cnt(n, PatchCounts{});
+    if (n) CK(hipMemcpyAsync(cnt.data(), d_cnt.p, n * sizeof(PatchCounts), hipMemcpyDeviceToHost, s));
+    CK(hipStreamSynchronize(s));
+    // scratch and output of every request, from the mark launch's counts
+    std::vector<PatchDesc> pd(n, PatchDesc{});
+    M->out_off.assign(n, 0);
+    uint64_t words = 0, bytes = 0, outb = 0;
+    for (size_t i = 0; i < n; i++) {
+        const PatchCounts &c = cnt[i];
+        const DecodeResult &br = B->res[doc[i]];
+        PatchDesc &d = pd[i];
+        d.skip = c.status;
+        // the StartBranch content is the checkout at `from`: the host's dtgpu_oplog_encode has it
+        if (!d.skip && c.n_front && (flags & DTGPU_ENCODE_STORE_START_BRANCH_CONTENT)) d.skip = DECODE_DEFER;
+        if (d.skip) continue;
+        d.n_pieces = c.n_pieces; d.n_par = c.n_par; d.n_ar = c.n_ar; d.n_op = c.n_op; d.n_lv = c.n_lv;
+        d.n_text = c.n_text; d.n_front = c.n_front;
+        d.doc_id_off = br.doc_id_off; d.doc_id_len = br.doc_id_len;
+        // records: a ContentIsKnown change inside an op-run piece splits it (only where content is missing)
+        const uint64_t oprec = uint64_t(c.n_op) + (hd[i].b_complete ? 0 : c.n_lv);
+        // bytes: an agent assignment run is three varints of <= 5 bytes; a txn its length, then per
+        // parent <= 5 bytes (local) or <= 10 (foreign agent and seq), 1 for ROOT; an op run <= 12
+        // (a 36-bit head, a 33-bit diff); the Version two varints per frontier LV; the names chunk
+        // lists at most every agent; PATCH_FIXED_BYTES covers the magic, the chunk headers and the CRC
+        const uint64_t c_aa = 15ull * c.n_ar + 16, c_tx = 6ull * c.n_pieces + 10ull * c.n_par + 16;
+        const uint64_t doc_id = br.doc_id_len == 0xFFFFFFFFu ? 0 : br.doc_id_len;
+        const uint64_t cap = PATCH_FIXED_BYTES + patch_lz_bound(c.n_text) + c.n_names + doc_id + 10ull * c.n_front + c_aa + 12 * oprec + c_tx;
+        if (oprec > 0x7FFFFFFFull || cap > 0x7FFFFFFFull) { d = PatchDesc{}; d.skip = DTGPU_ERR_CAPACITY; continue; }
+        d.c_oprec = uint32_t(oprec); d.c_aa = uint32_t(c_aa); d.c_tx = uint32_t(c_tx); d.out_cap = uint32_t(cap);
+        d.w_off = words; words += patch_words(hd[i].b_n_ent, hd[i].b_n_agents, d);
+        d.b_off = bytes; bytes = (bytes + patch_bytes(d) + 15) & ~uint64_t(15);
+        d.out_off = outb; outb = align256(outb + cap);
+        M->out_off[i] = d.out_off;
+    }
+    CK(d_w.alloc(words));
+    CK(d_b.alloc(bytes));
+    CK(M->out.alloc(outb));
+    CK(d_pd.upload(pd, s));
+    P.docs = d_pd.p; P.w = d_w.p; P.b = d_b.p; P.out = M->out.p;
+    CK(hipEventRecord(own.e[2], s));
+    if (launch_patch_build(P, s)) return DTGPU_ERR_HIP;
+    CK(hipEventRecord(own.e[3], s));
+    M->res.assign(n, PatchResult{});
+    if (n) CK(hipMemcpyAsync(M->res.data(), d_res.p, n * sizeof(PatchResult), hipMemcpyDeviceToHost, s));
+    CK(hipStreamSynchronize(s));
+    float t0 = 0, t1 = 0;
+    CK(hipEventElapsedTime(&t0, own.e[0], own.e[1]));
+    CK(hipEventElapsedTime(&t1, own.e[2], own.e[3]));
+#undef CK
+    M->n_front.assign(n, 0);
+    for (size_t i = 0; i < n; i++) M->n_front[i] = cnt[i].status ? 0u : cnt[i].n_front;
+    M->form.assign(n, 0);
+    for (size_t i = 0; i < n; i++) M->form[i] = cnt[i].form;
+    M->mark_ms = t0;
+    M->build_ms = t1;
+    if (ms) *ms = t0 + t1;
+    *out = guard.release();
+    return DTGPU_OK;
+}
+
+size_t dtgpu_patches_size(const dtgpu_patches *p) { return p ? p->n : 0; }
+
+dtgpu_status dtgpu_patches_result(const dtgpu_patches *p, size_t i, uint64_t *frontier, size_t cap, size_t *n_frontier) {
+    if (n_frontier) *n_frontier = 0;
+    if (!p || i >= p->n || (!frontier && cap)) return DTGPU_ERR_ARG;
+    const size_t k = p->n_front[i];
+    if (n_frontier) *n_frontier = k;
+    if (k && cap) {
+        std::vector<uint32_t> f(k);
+        if (hipMemcpy(f.data(), p->front.p + uint64_t(DECODE_MAX_FRONTIER) * i, k * 4, hipMemcpyDeviceToHost) != hipSuccess)
+            return DTGPU_ERR_HIP;
+        for (size_t j = 0; j < k && j < cap; j++) frontier[j] = f[j];
+    }
+    return dtgpu_status(p->res[i].status);
+}
+
+dtgpu_status dtgpu_patches_get(const dtgpu_patches *p, size_t i, uint8_t *out, size_t cap, size_t *out_len) {
+    if (out_len) *out_len = 0;
+    if (!p || i >= p->n) return DTGPU_ERR_ARG;
+    const PatchResult &r = p->res[i];
+    if (r.status) return dtgpu_status(r.status);
+    if (out_len) *out_len = r.len;
+    if (!out) return DTGPU_OK;
+    if (cap < r.len) return DTGPU_ERR_ARG;
+    if (r.len && hipMemcpy(out, p->out.p + p->out_off[i], r.len, hipMemcpyDeviceToHost) != hipSuccess) return DTGPU_ERR_HIP;
+    return DTGPU_OK;
+}
+
+dtgpu_status dtgpu_patches_profile(const dtgpu_patches *p, size_t i, uint32_t out[12]) {
+    if (!p || i >= p->n || !out) return DTGPU_ERR_ARG;
+    const PatchResult &r = p->res[i];
+    out[0] = p->form[i];
+    out[1] = uint32_t(p->mark_ms * 1000.f);
+    out[2] = uint32_t(p->build_ms * 1000.f);
+    out[3] = r.n_walk;
+    for (int k = 0; k < 7; k++) out[4 + k] = r.cyc[k];
+    out[11] = 0;
+    return DTGPU_OK;
+}
+
+void dtgpu_patches_free(dtgpu_patches *p) { delete p; }
 
 size_t dtgpu_decode_size(const dtgpu_decoded *D) { return D ? D->n : 0; }
 

@@ -226,6 +226,14 @@ def lib():
     L.dtgpu_decode_history.argtypes = [vp, ctypes.POINTER(ctypes.c_uint32), pu64, ctypes.POINTER(sz), sz,
                                        ctypes.POINTER(ctypes.c_float), ctypes.POINTER(vp)]
     L.dtgpu_decode_history_result.argtypes = [vp, sz, pu64, sz, ctypes.POINTER(sz)]
+    L.dtgpu_decode_encode_from.argtypes = [vp, ctypes.POINTER(ctypes.c_uint32), pu64, ctypes.POINTER(sz), sz,
+                                           ctypes.c_uint32, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(vp)]
+    L.dtgpu_patches_size.argtypes = [vp]
+    L.dtgpu_patches_size.restype = sz
+    L.dtgpu_patches_result.argtypes = [vp, sz, pu64, sz, ctypes.POINTER(sz)]
+    L.dtgpu_patches_get.argtypes = [vp, sz, ctypes.c_char_p, sz, ctypes.POINTER(sz)]
+    L.dtgpu_patches_profile.argtypes = [vp, sz, ctypes.POINTER(ctypes.c_uint32)]
+    L.dtgpu_patches_free.argtypes = [vp]
     L.dtgpu_batch_create_decoded.argtypes = [vp, ctypes.POINTER(vp)]
     L.dtgpu_graph_queries.argtypes = [ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(sz), sz,
                                       ctypes.POINTER(GraphQuery), sz, ctypes.POINTER(ctypes.c_int64), sz,
@@ -969,6 +977,26 @@ class DecodeBatch:
         st = lib().dtgpu_decode_history_result(self._h, i, buf, 64, ctypes.byref(k))
         return st, list(buf[:k.value])
 
+    def encode_from(self, docs, versions, opts=None):
+        """ListOpLog::encode_from(opts, versions[i]) of document docs[i] for a whole batch, on the GPU
+        (dtgpu_decode_encode_from): the `.dt` patch that takes a peer at versions[i] (any set of LVs;
+        [] is ROOT) to this document's tip.  opts defaults to ENCODE_PATCH.  Returns a PatchBatch."""
+        n = len(docs)
+        if len(versions) != n:
+            raise ValueError("one version per document index")
+        flat, off = [], [0]
+        for v in versions:
+            flat.extend(int(x) for x in v)
+            off.append(len(flat))
+        d = (ctypes.c_uint32 * max(n, 1))(*[int(x) for x in docs])
+        pv, _ = _u64s(flat)
+        po = (ctypes.c_size_t * (n + 1))(*off)
+        ms = ctypes.c_float()
+        h = ctypes.c_void_p()
+        flags = (opts or ENCODE_PATCH).flags()
+        _check(lib().dtgpu_decode_encode_from(self._h, d, pv, po, n, flags, ctypes.byref(ms), ctypes.byref(h)))
+        return PatchBatch(h, n, ms.value)
+
     def checkout_versions(self, docs, versions):
         """ListOpLog::checkout(versions[i]) of document docs[i] for a whole batch: the histories
         projected on the GPU (history), then one device-staged checkout batch.  Returns the
@@ -1013,6 +1041,50 @@ class DecodeBatch:
 
     def bytes_out(self) -> int:
         return lib().dtgpu_decode_bytes(self._h, 1)
+
+
+class PatchBatch:
+    """The patches of one DecodeBatch.encode_from call (dtgpu_patches), resident on the device."""
+
+    def __init__(self, handle, n, last_ms):
+        self._h, self.n, self.last_ms = handle, n, last_ms
+
+    def __len__(self):
+        return self.n
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            lib().dtgpu_patches_free(h)
+            self._h = None
+
+    def _result(self, i):
+        k = ctypes.c_size_t()
+        buf = (ctypes.c_uint64 * 64)()
+        st = lib().dtgpu_patches_result(self._h, i, buf, 64, ctypes.byref(k))
+        return st, list(buf[:k.value])
+
+    def status(self, i) -> int:
+        return self._result(i)[0]
+
+    def frontier(self, i):
+        """Request i reduced to a frontier, in the base document's LVs, ascending."""
+        return self._result(i)[1]
+
+    def profile(self, i):
+        """dtgpu_patches_profile: [mark form (1 LDS, 2 HBM), mark us, build us, walk steps, then --
+        when DTGPU_PATCH_PROF was set at the call -- the build wave's cycles in its seven phases]."""
+        out = (ctypes.c_uint32 * 12)()
+        _check(lib().dtgpu_patches_profile(self._h, i, out))
+        return list(out)
+
+    def patch(self, i) -> bytes:
+        """Request i's `.dt` patch; ParseError carries a non-zero status."""
+        n = ctypes.c_size_t()
+        _check(lib().dtgpu_patches_get(self._h, i, None, 0, ctypes.byref(n)))
+        buf = ctypes.create_string_buffer(max(1, n.value))
+        _check(lib().dtgpu_patches_get(self._h, i, buf, n.value, ctypes.byref(n)))
+        return buf.raw[:n.value]
 
 
 GQ_KINDS = {"diff": 0, "conflict": 1, "contains": 2, "dominators": 3, "diff_level": 4, "conflict_level": 5}

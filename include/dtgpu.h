@@ -465,6 +465,45 @@ dtgpu_status dtgpu_decode_history(const dtgpu_decoded *base, const uint32_t *doc
  * document's LVs, ascending. */
 dtgpu_status dtgpu_decode_history_result(const dtgpu_decoded *hist, size_t i, uint64_t *frontier, size_t cap,
                                          size_t *n_frontier);
+/* ListOpLog::encode_from(opts, from) (src/list/encoding/encode_oplog.rs:404-747) for a batch:
+ * output i is the `.dt` patch holding the ops of resident document doc[i] that are not in
+ * Hist(versions[version_off[i] .. version_off[i+1])), built on the GPU by one wavefront per request
+ * (dt_patch.hip): the history mark sweep, a SpanningTreeWalker over the new ops alone
+ * (txn_trace.rs:114-333), the reference's run mergers, LZ4 and CRC-32C.  `base` (after
+ * dtgpu_decode_run, a dtgpu_decode_add result or a history handle) is unchanged; doc[i] may repeat,
+ * in any order (DTGPU_ERR_ARG when one is >= dtgpu_decode_size(base)).  A request is any set of the
+ * document's LVs -- unsorted, with duplicates, not a frontier; the empty request is ROOT.  flags:
+ * DTGPU_ENCODE_STORE_INSERTED_CONTENT and DTGPU_ENCODE_COMPRESS_CONTENT as in dtgpu_oplog_encode.
+ * For every request with status 0 the bytes equal dtgpu_oplog_encode(host oplog of that document,
+ * the reduced frontier, flags), byte for byte.  Per-request status: the base document's own when
+ * that is not 0; DTGPU_ERR_ARG for an LV >= the document's LV count; DTGPU_ERR_CHECKOUT where the
+ * host encoder returns it (content is to be stored and an insert's content is unknown);
+ * DTGPU_DECODE_DEFER when the reduced frontier is wider than 64, and for
+ * DTGPU_ENCODE_STORE_START_BRANCH_CONTENT on a non-ROOT request (the checkout at `from` stays with
+ * dtgpu_oplog_encode; the bit does nothing for a ROOT request); DTGPU_ERR_CAPACITY when a
+ * reservation proves too small.  A failed request never fails the batch.  *ms = the two patch
+ * kernels' time (HIP events).  All of a request's walk and record scratch is in HBM, sized from the
+ * base's entry and parent counts: no size limit and no deferral class of its own. */
+typedef struct dtgpu_patches dtgpu_patches;
+dtgpu_status dtgpu_decode_encode_from(const dtgpu_decoded *base, const uint32_t *doc, const uint64_t *versions,
+                                      const size_t *version_off, size_t n, uint32_t flags, float *ms,
+                                      dtgpu_patches **out);
+size_t dtgpu_patches_size(const dtgpu_patches *p);
+/* Request i's status, and its request reduced to a frontier (find_dominators,
+ * src/causalgraph/graph/tools.rs:545-578), in the base document's LVs, ascending. */
+dtgpu_status dtgpu_patches_result(const dtgpu_patches *p, size_t i, uint64_t *frontier, size_t cap, size_t *n_frontier);
+/* Request i's bytes (out == NULL: the size in *out_len; DTGPU_ERR_ARG when cap is too small);
+ * returns the request's status. */
+dtgpu_status dtgpu_patches_get(const dtgpu_patches *p, size_t i, uint8_t *out, size_t cap, size_t *out_len);
+/* Which form request i's mark sweep took, and where its time went: out[0] = 1 when the sweep's
+ * per-entry words were kept in LDS, 2 in HBM scratch (the rule and the DTGPU_HISTORY_LDS_ENTRIES
+ * override of dtgpu_decode_history), 0 when the base document was not marked; out[1], out[2] = the
+ * mark and build launches' us (whole batch); out[3] = walk steps.  Only when DTGPU_PATCH_PROF was
+ * set in the environment at call time (0 otherwise): out[4..10] = the build wave's core-clock
+ * cycles in pieces + edges, the walk, agent and txn records, op runs, the text gather, LZ4,
+ * write + CRC.  out[11] = 0. */
+dtgpu_status dtgpu_patches_profile(const dtgpu_patches *p, size_t i, uint32_t out[12]);
+void dtgpu_patches_free(dtgpu_patches *p);
 /* A device-staged checkout batch over a decoded handle (consumed, also on failure): decoded here
  * unless it already holds merged oplogs; then as dtgpu_batch_create_device. */
 dtgpu_status dtgpu_batch_create_decoded(dtgpu_decoded *dec, dtgpu_batch **out);
