@@ -825,9 +825,10 @@ DEV void plan_doc_split(P &p, PlanResult *res) {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    // each chain's dense-table slice, in LDS (the todo stack's space: phase A is done)
+    // each chain's dense-table slice, in LDS (the todo stack's space: phase A is done): A + 1
+    // offsets, one more than the lanes at 64 chains
     uint32_t *sdoff = reinterpret_cast<uint32_t *>(p.todo);
-    if (l <= p.A) sdoff[l] = p.doff[l];
+    for (uint32_t a = l; a <= p.A; a += 64) sdoff[a] = p.doff[a];
     fence_wave();
     // ---- phase B: per step, lane = step ----
     const uint32_t A = p.A;

@@ -141,6 +141,19 @@ def test_device_encoder_reports_deferred_documents():
         assert st == 80
 
 
+def test_device_encoder_defers_exactly_past_64_chains():
+    """Beside it, the fans on the limit itself (wide_docs.py: W branches are W causal chains): the
+    64-fan is encoded on the device, byte for byte; the 65-fan is handed back with DECODE_DEFER."""
+    import wide_docs as W
+    ok = G.dt_bytes("friendsforever")
+    at64, at65 = W.fan(64, merge=True).encode(), W.fan(65, merge=True).encode()
+    b = dt_amd.Batch(docs=[ok, at64, ok, at65, ok], staging="device")
+    b.encode()
+    assert [b.encoded_status(i) for i in range(5)] == [0, 0, 0, dt_amd.DECODE_DEFER, 0]
+    for i, d in ((0, ok), (1, at64), (2, ok), (4, ok)):
+        assert b.encoded(i) == dt_amd.ListOpLog.load_from(d).encode(), i
+
+
 def test_device_encoder_random_documents():
     """64 pairwise-merge synthetic documents of varied size and agent count (SURVEY 8(d)4's
     generator), Unicode variants among them, encoded in one batch: every document's bytes equal
