@@ -797,6 +797,11 @@ struct CRuns {               // ContentIsKnown run iterator (ReadPatchContentIte
     uint32_t pb, pb_known;
     uint64_t pb_len;
     Rd pb_s;
+    // field by field: a whole-struct fill or copy under a branch keeps the struct in private memory
+    __device__ __forceinline__ void open(const Rd &t, uint32_t asc, const VQ &q) {
+        present = 1; ascii = asc; runs = q; text = t; t0 = t.p;
+        pb = 0; pb_known = 0; pb_len = 0; pb_s = Rd{0, 0, 0};
+    }
 };
 
 template <bool SIZE>
@@ -1752,6 +1757,316 @@ __device__ __forceinline__ FastOut fast_runs(VQ qav, VQ qtp, VQ runs, uint32_t t
     return fo;
 }
 
+// ---------------------------------------------------------------------------------------------
+// the `.dt` file walk: the steps of the exact path, shared by decode_doc (load_from), add_doc
+// (decode_and_add) and lz4_kernel (the header).  Each returns the status the host decoder reports
+// at that step; the callers keep the order of the steps, their own capacity checks and their
+// output sinks.  What differs by caller stays with the caller: FileInfo / agent names,
+// StartBranch, the OpParents loops and decode_doc's fast path.
+// ---------------------------------------------------------------------------------------------
+// magic and protocol version; r: the chunks after them
+__device__ __forceinline__ int file_open(Ctx &C, uint32_t len, Rd &r) {
+    if (len < 8) return UnexpectedEOF;
+    const char *magic = "DMNDTYPS";
+    for (uint32_t i = 0; i < 8; i++)
+        if (C.byte(0, i) != uint32_t(uint8_t(magic[i]))) return InvalidMagic;
+    r = Rd{0, 8, len - 8};
+    uint64_t pv;
+    TRY(C.u64v(r, pv));
+    return pv != 0 ? UnsupportedProtocolVersion : S_OK;
+}
+
+// the optional LZ4 chunk: its compressed block c and the claimed decompressed length
+__device__ __forceinline__ int lz4_chunk(Ctx &C, Rd &r, bool &found, Rd &c, uint64_t &ulen) {
+    TRY(C.chunk_if(r, 5, found, c));
+    if (!found) return S_OK;
+    TRY(C.u64v(c, ulen));
+    if (ulen > (uint64_t(1) << 34)) return LZ4DecompressionError;
+    // an LZ4 block expands at most ~255x: a larger claim cannot decompress exactly
+    if (ulen > 255ull * c.n + 64) return LZ4DecompressionError;
+    return S_OK;
+}
+
+// the PatchContent directory (decode_oplog.rs:383-425): the content iterators, then the
+// OpVersions, OpTypeAndPosition and OpParents streams as varint queues.  ins / del: zeroed by
+// the caller, opened here where the file has the chunk.
+template <bool SIZE>
+__device__ __forceinline__ int patch_chunks(Ctx &C, Rd &r, Rd &comp, bool has_comp, Rd &pc, CRuns &ins, CRuns &del,
+                                            uint32_t &cik_bytes, VQ &qav, VQ &qtp, VQ &qhist) {
+    TRY(C.expect_chunk(r, 20, pc));
+    cik_bytes = 0;
+    for (;;) {
+        bool found; Rd ch;
+        TRY(C.chunk_if(pc, 24, found, ch));
+        if (!found) break;
+        uint64_t tag;
+        TRY(C.u32v(ch, tag));
+        if (tag > 1) return InvalidContent;
+        Rd text, runs;
+        uint32_t ascii;
+        TRY(content_str<SIZE>(C, ch, comp, has_comp, text, ascii));
+        TRY(C.expect_chunk(ch, 25, runs));
+        cik_bytes += runs.n;
+        if (tag == 0) ins.open(text, ascii, vq_make(C.in, runs));
+        else del.open(text, ascii, vq_make(C.in, runs));
+    }
+    Rd av, tp, hist;
+    TRY(C.expect_chunk(pc, 21, av));
+    TRY(C.expect_chunk(pc, 22, tp));
+    TRY(C.expect_chunk(pc, 23, hist));
+    qav = vq_make(C.in, av); qtp = vq_make(C.in, tp); qhist = vq_make(C.in, hist);
+    return S_OK;
+}
+
+// one OpVersions record: file agent + 1 (0 is invalid), run length, seq jump
+__device__ __forceinline__ int arun_next(VQ &qav, uint32_t *vs, uint64_t &n, uint64_t &alen, int64_t &jump) {
+    jump = 0;
+    TRY(vq_pop(qav, n, vs));
+    const bool has_jump = n & 1;
+    n >>= 1;
+    TRY(vq_pop(qav, alen, vs));
+    if (has_jump) TRY(vq_zigzag(qav, jump, vs));
+    return S_OK;
+}
+
+// The pending file op (ReadPatchesIter, decode_oplog.rs:289-337): the OpTypeAndPosition record
+// being handed out piece by piece.
+struct FileOp {
+    bool have, del, fwd;
+    uint64_t len;
+    int64_t start, last_cursor;
+    __device__ __forceinline__ void init() { have = false; del = false; fwd = true; len = 0; start = 0; last_cursor = 0; }
+    __device__ __forceinline__ int next(VQ &qtp, uint32_t *vs) {
+        if (!qtp.left()) return InvalidLength;
+        uint64_t x;
+        TRY(vq_pop(qtp, x, vs));
+        const bool has_length = x & 1; x >>= 1;
+        const bool diff_nz = x & 1; x >>= 1;
+        const bool is_del = x & 1; x >>= 1;
+        int64_t diff = 0;
+        bool f = true;
+        uint64_t l;
+        if (has_length) {
+            if (is_del) { f = x & 1; x >>= 1; }
+            if (diff_nz) TRY(vq_zigzag(qtp, diff, vs));
+            l = x;
+        } else {
+            l = 1;
+            diff = int64_t(x >> 1) * ((x & 1) ? -1 : 1);
+        }
+        const int64_t raw = int64_t(uint64_t(last_cursor) + uint64_t(diff));
+        int64_t st, raw_end;
+        if (!is_del) { st = raw; raw_end = raw + int64_t(l); }
+        else if (f) { st = raw; raw_end = raw; }
+        else { st = raw - int64_t(l); raw_end = raw - int64_t(l); }
+        last_cursor = raw_end;
+        if (l == 0) return ErrCheckout;   // assert!(max_len > 0)
+        len = l; start = st; del = is_del; fwd = f; have = true;
+        return S_OK;
+    }
+    // the position of the next `take` items; out-of-range positions are left to the host decoder
+    __device__ __forceinline__ int piece(uint64_t take, uint32_t &ppos, bool &pfwd) const {
+        int64_t p;
+        pfwd = true;
+        if (!del) p = start;
+        else if (fwd) p = start;
+        else { p = start + int64_t(len) - int64_t(take); pfwd = false; }
+        if (p < 0 || uint64_t(p) >= LIM31) return Defer;
+        ppos = uint32_t(p);
+        return S_OK;
+    }
+    __device__ __forceinline__ void consume(uint64_t take) {
+        if (!del) start += int64_t(take);
+        len -= take;
+        if (!len) have = false;
+    }
+};
+
+// The content run under the next piece of an op (ContentRuns::next with SplitableSpan truncate):
+// take shrinks to the run's length, a longer run's remainder is pushed back.  known / cs: the
+// piece's content is in the file / its bytes.  ci: the caller's copy of the op kind's iterator
+// (selected by value and stored back there: no dynamically indexed private memory).
+__device__ __forceinline__ int content_take(Ctx &C, CRuns &ci, uint64_t &take, bool &known, Rd &cs, uint32_t *vs) {
+    known = false;
+    cs = Rd{0, 0, 0};
+    if (ci.present) {
+        bool has, cknown; uint64_t clen;
+        TRY(cruns_next(C, ci, has, clen, cknown, cs, vs));
+        if (!has) return InvalidLength;
+        if (clen < take) take = clen;
+        if (clen > take) {   // push the remainder back
+            uint32_t b = 0;
+            if (cknown) {
+                uint64_t c2;
+                walk_chars(C.ptr(cs.s) + cs.p, cs.n, take, ci.ascii, b, c2);
+            }
+            ci.pb = 1;
+            ci.pb_len = clen - take; ci.pb_known = cknown;
+            ci.pb_s = cknown ? Rd{cs.s, cs.p + b, cs.n - b} : Rd{cs.s, cs.p, 0};
+            cs.n = b;
+        }
+        known = cknown;
+    }
+    return take ? S_OK : ErrCheckout;
+}
+
+// per-LV byte offsets of a known insert piece (n_bytes of text at src, placed at content offset
+// base): ASCII one per byte, else the char starts by ballot
+__device__ __forceinline__ void place_offsets(uint32_t *cbyte, uint32_t lv, uint64_t take, const uint8_t *src,
+                                              uint32_t n_bytes, uint32_t base, bool ascii) {
+    if (ascii) {
+        for (uint64_t i = lane(); i < take; i += 64) cbyte[lv + i] = base + uint32_t(i);
+        return;
+    }
+    uint32_t cnt = 0;
+    for (uint32_t i = 0; i < n_bytes; i += 64) {
+        const uint32_t j = i + lane();
+        const bool st = j < n_bytes && (src[j] & 0xC0u) != 0x80u;
+        const uint64_t m = ballot(st);
+        if (st) cbyte[lv + cnt + popc(m & lt_mask())] = base + j;
+        cnt += popc(m);
+    }
+}
+// content unknown (deleted items, inserts without text)
+__device__ __forceinline__ void place_unknown(uint32_t *cbyte, uint32_t lv, uint64_t take) {
+    for (uint64_t i = lane(); i < take; i += 64) cbyte[lv + i] = 0xFFFFFFFFu;
+}
+
+// The pending op run (RLE append, op_metrics.rs:235-293): push_* extend it where the piece
+// continues it; where not, the caller flushes it to its own sink and starts the next.
+struct OpRun {
+    uint32_t valid, lv, len, pos, kind, fwd;
+    __device__ __forceinline__ void init() { valid = 0; lv = 0; len = 0; pos = 0; kind = 0; fwd = 0; }
+    __device__ __forceinline__ void load(const uint4 &o) {
+        valid = 1; lv = o.x; len = o.y; pos = o.z; kind = o.w & 1u; fwd = (o.w >> 1) & 1u;
+    }
+    __device__ __forceinline__ uint4 quad() const { return make_uint4(lv, len, pos, kind | (fwd << 1)); }
+    __device__ __forceinline__ void start(uint32_t lv_, uint32_t ln, uint32_t p, bool is_del, bool pfwd) {
+        valid = 1; lv = lv_; len = ln; pos = p; kind = is_del ? 1u : 0u; fwd = pfwd ? 1u : 0u;
+    }
+    __device__ __forceinline__ bool push_ins(uint32_t lv_, uint32_t ln, uint32_t p) {
+        if (!(valid && kind == 0 && lv + len == lv_ && uint64_t(pos) + len == uint64_t(p))) return false;
+        len += ln;
+        return true;
+    }
+    __device__ __forceinline__ bool push_del(uint32_t lv_, uint32_t ln, uint32_t p, bool pfwd) {
+        if (!(valid && kind == 1 && lv + len == lv_)) return false;
+        if ((len == 1 || fwd) && (ln == 1 || pfwd) && p == pos) {
+            len += ln; fwd = 1;
+            return true;
+        }
+        if ((len == 1 || !fwd) && (ln == 1 || !pfwd) && uint64_t(p) + ln == pos) {
+            pos = p; len += ln; fwd = 0;
+            return true;
+        }
+        return false;
+    }
+};
+
+// both content iterators must be exhausted
+__device__ __forceinline__ int content_done(Ctx &C, CRuns &ins, CRuns &del, uint32_t *vs) {
+    if (ins.present) {
+        bool has, kn; uint64_t l; Rd s;
+        const int e = cruns_next(C, ins, has, l, kn, s, vs);
+        if (e || has) return InvalidContent;
+    }
+    if (del.present) {
+        bool has, kn; uint64_t l; Rd s;
+        const int e = cruns_next(C, del, has, l, kn, s, vs);
+        if (e || has) return InvalidContent;
+    }
+    return S_OK;
+}
+
+// the CRC chunk over everything before it (decode_oplog.rs:940-955)
+__device__ __forceinline__ int crc_check(Ctx &C, Rd &r, uint32_t len, bool ignore_crc, const uint32_t *table,
+                                         const uint32_t *x2n) {
+    const uint32_t reader_len = r.n;
+    bool found; Rd c;
+    TRY(C.chunk_if(r, 100, found, c));
+    if (found && !ignore_crc) {
+        if (c.n < 4) return UnexpectedEOF;
+        const uint32_t want = C.byte(0, c.p) | (C.byte(0, c.p + 1) << 8) | (C.byte(0, c.p + 2) << 16) |
+                              (C.byte(0, c.p + 3) << 24);
+        if (crc32c_par(C.in, len - reader_len, table, x2n) != want) return ChecksumFailed;
+    }
+    return S_OK;
+}
+
+// Op runs split at graph-entry boundaries (HostOpLog::finish): pre[0, n_pre) to ops from
+// first_out on, n_out the count after.  One run per lane: its first entry by bisection, its
+// pieces (one per entry it touches) at a prefix-sum offset; a run rarely spans entries, so the
+// per-lane loops are short.  Runs and entries are both in LV order.
+__device__ __forceinline__ int split_at_entries(const uint4 *pre, uint32_t n_pre, const uint2 *ent, uint32_t n_ent,
+                                                uint4 *ops, uint32_t first_out, uint32_t cap, uint32_t &n_out) {
+    uint32_t nout = first_out, ebase = 0;   // ebase: the entry of the previous chunk's last run
+    for (uint32_t b0 = 0; b0 < n_pre; b0 += 64) {
+        const uint32_t i = b0 + lane();
+        const bool live = i < n_pre;
+        const uint4 q = live ? pre[i] : make_uint4(0, 0, 0, 0);
+        // a run's first entry is at or after ebase: search the 64 entries from there in
+        // registers, HBM only past that window
+        const uint32_t we = ebase + lane() < n_ent ? ent[ebase + lane()].y : 0xFFFFFFFFu;
+        uint32_t c = 0;
+#pragma unroll
+        for (uint32_t st = 32; st >= 1; st >>= 1)
+            if (uint32_t(__shfl(int(we), int(c + st - 1))) <= q.x) c += st;
+        if (c == 63 && rdl(we, 63) <= q.x) c = 64;
+        uint32_t lo = ebase + c, hi = live && c == 64 ? n_ent : lo;
+        while (lo < hi) {
+            const uint32_t m = (lo + hi) >> 1;
+            if (ent[m].y <= q.x) lo = m + 1; else hi = m;
+        }
+        uint32_t npc = 0;
+        if (live) {
+            npc = 1;
+            const uint32_t end = q.x + q.y;
+            for (uint32_t e = lo; e < n_ent && ent[e].y < end; e++) npc++;
+        }
+        const uint32_t incl = scan_incl(npc);
+        const uint32_t tot = rdl(incl, 63);
+        if (uint64_t(nout) + tot > cap) return ErrCapacity;
+        if (live) {
+            uint32_t rlv = q.x, rlen = q.y, rpos = q.z, e = lo, k = nout + incl - npc;
+            const uint32_t kf = q.w, kind = kf & 1u, fwd = kf >> 1;
+            while (rlen) {
+                const uint32_t cut = e < n_ent ? ent[e].y : rlv + rlen;
+                const uint32_t mm = rlen < cut - rlv ? rlen : cut - rlv;
+                uint32_t apos = rpos;
+                if (kind == 0) rpos += mm;
+                else if (!fwd) apos = rpos + rlen - mm;
+                ops[k++] = make_uint4(rlv, mm, apos, kf);
+                rlv += mm;
+                rlen -= mm;
+                if (rlv >= cut) e++;
+            }
+        }
+        nout += tot;
+        ebase = rdl(lo, min(n_pre - 1 - b0, 63u));
+    }
+    n_out = nout;
+    return S_OK;
+}
+
+// the LDS prefix both decoder kernels carve alike (F: max file agents); the agent tables follow
+// from the returned pointer, per kernel
+__device__ __forceinline__ uint32_t *lds_common(Lds &L, uint32_t *lds, uint32_t F) {
+    L.crc = lds;
+    L.fr = lds + 256;
+    L.vq = lds + 320;
+    L.fmap = lds + 512;
+    L.fseq = L.fmap + F;
+    return L.fseq + F;
+}
+__device__ __forceinline__ void crc_table(uint32_t *crc) {
+    for (uint32_t i = lane(); i < 256; i += 64) {
+        uint32_t c = i;
+        for (int k = 0; k < 8; k++) c = (c & 1u) ? (c >> 1) ^ CRC_POLY : c >> 1;
+        crc[i] = c;
+    }
+    __syncthreads();
+}
+
 template <bool SIZE>
 __device__ __forceinline__ int decode_doc(const DecodeParams &P, const DecodeDesc &D, DecodeResult &R, const Lds &L,
                                           uint32_t doc) {
@@ -1780,28 +2095,16 @@ __device__ __forceinline__ int decode_doc(const DecodeParams &P, const DecodeDes
         R.prof[k] += uint32_t(t - t_prev);
         t_prev = t;
     };
-    if (len < 8) return UnexpectedEOF;
-    {
-        const char *magic = "DMNDTYPS";
-        for (uint32_t i = 0; i < 8; i++)
-            if (C.byte(0, i) != uint32_t(uint8_t(magic[i]))) return InvalidMagic;
-    }
-    Rd r{0, 8, len - 8};
-    uint64_t pv;
-    TRY(C.u64v(r, pv));
-    if (pv != 0) return UnsupportedProtocolVersion;
+    Rd r;
+    TRY(file_open(C, len, r));
 
     Rd comp{SRC_LZ, 0, 0};
     bool has_comp = false;
     {
         bool found; Rd c;
-        TRY(C.chunk_if(r, 5, found, c));
+        uint64_t ulen;
+        TRY(lz4_chunk(C, r, found, c, ulen));
         if (found) {
-            uint64_t ulen;
-            TRY(C.u64v(c, ulen));
-            if (ulen > (uint64_t(1) << 34)) return LZ4DecompressionError;
-            // an LZ4 block expands at most ~255x: a larger claim cannot decompress exactly
-            if (ulen > 255ull * c.n + 64) return LZ4DecompressionError;
             if (SIZE) {
                 R.lz_len = uint32_t(ulen);
             } else {
@@ -1901,47 +2204,23 @@ __device__ __forceinline__ int decode_doc(const DecodeParams &P, const DecodeDes
         }
     }
     Rd pc;
-    TRY(C.expect_chunk(r, 20, pc));
     CRuns ins{}, del{};
-    uint32_t cik_bytes = 0;
-    for (;;) {
-        bool found; Rd ch;
-        TRY(C.chunk_if(pc, 24, found, ch));
-        if (!found) break;
-        uint64_t tag;
-        TRY(C.u32v(ch, tag));
-        if (tag > 1) return InvalidContent;
-        CRuns it{};
-        it.present = 1;
-        TRY(content_str<SIZE>(C, ch, comp, has_comp, it.text, it.ascii));
-        Rd runs;
-        TRY(C.expect_chunk(ch, 25, runs));
-        it.runs = vq_make(C.in, runs);
-        it.t0 = it.text.p;
-        cik_bytes += runs.n;
-        if (tag == 0) ins = it; else del = it;
-    }
-    Rd av, tp, hist;
-    TRY(C.expect_chunk(pc, 21, av));
-    TRY(C.expect_chunk(pc, 22, tp));
-    TRY(C.expect_chunk(pc, 23, hist));
-    VQ qav = vq_make(C.in, av), qtp = vq_make(C.in, tp), qhist = vq_make(C.in, hist);
+    uint32_t cik_bytes;
+    VQ qav, qtp, qhist;
+    TRY(patch_chunks<SIZE>(C, r, comp, has_comp, pc, ins, del, cik_bytes, qav, qtp, qhist));
     uint32_t *vs = L.vq;
     prof_mark(1);
 
     if (SIZE) {   // OpVersions: LV count and agent runs
         uint64_t lv = 0;
         uint32_t runs = 0;
-        R.tp_bytes = tp.n;
+        R.tp_bytes = qtp.len;
         R.cik_bytes = cik_bytes;
-        R.hist_bytes = hist.n;
+        R.hist_bytes = qhist.len;
         while (qav.left()) {
             uint64_t n, alen;
-            int64_t jump = 0;
-            TRY(vq_pop(qav, n, vs));
-            const bool hj = n & 1;
-            TRY(vq_pop(qav, alen, vs));
-            if (hj) TRY(vq_zigzag(qav, jump, vs));
+            int64_t jump;
+            TRY(arun_next(qav, vs, n, alen, jump));
             lv += alen;
             runs++;
             R.raw_aruns = runs;   // partial counts size a pass that fails later
@@ -1958,14 +2237,12 @@ __device__ __forceinline__ int decode_doc(const DecodeParams &P, const DecodeDes
     Quads qa, qp;
     qa.init(); qp.init();
     uint32_t ca_valid = 0, ca_lv = 0, ca_len = 0, ca_agent = 0, ca_seq = 0;   // pending agent run
-    uint32_t cr_valid = 0, cr_lv = 0, cr_len = 0, cr_pos = 0, cr_kind = 0, cr_fwd = 0;   // pending op run
+    OpRun cr;   // pending op run
+    cr.init();
     uint64_t n_lv = 0, next_assign = 0;
     uint32_t ins_size = 0, complete = 1, all_ascii = 1;
-    int64_t last_cursor = 0;
-    bool have_op = false;
-    uint64_t op_len = 0;
-    int64_t op_start = 0;
-    bool op_del = false, op_fwd = true;
+    FileOp op;
+    op.init();
 
     auto flush_arun = [&]() -> int {
         if (!ca_valid) return S_OK;
@@ -1974,13 +2251,11 @@ __device__ __forceinline__ int decode_doc(const DecodeParams &P, const DecodeDes
         return S_OK;
     };
     auto flush_op = [&]() -> int {
-        if (!cr_valid) return S_OK;
+        if (!cr.valid) return S_OK;
         if (qp.count() >= D.pre_cap) return int(ErrCapacity);
-        qp.push(cr_lv, cr_len, cr_pos, cr_kind | (cr_fwd << 1), O.pre);
+        const uint4 q = cr.quad();
+        qp.push(q.x, q.y, q.z, q.w, O.pre);
         return S_OK;
-    };
-    auto fill_cbyte = [&](uint64_t lv0, uint64_t k, uint32_t v) {
-        for (uint64_t i = lane(); i < k; i += 64) O.cbyte[lv0 + i] = v;
     };
 
     uint32_t fill_jobs = 0;   // deferred fill jobs of a long document (fill_kernel)
@@ -2041,12 +2316,8 @@ __device__ __forceinline__ int decode_doc(const DecodeParams &P, const DecodeDes
 
     while (qav.left()) {
         uint64_t n, alen;
-        int64_t jump = 0;
-        TRY(vq_pop(qav, n, vs));
-        const bool has_jump = n & 1;
-        n >>= 1;
-        TRY(vq_pop(qav, alen, vs));
-        if (has_jump) TRY(vq_zigzag(qav, jump, vs));
+        int64_t jump;
+        TRY(arun_next(qav, vs, n, alen, jump));
         if (n == 0 || n - 1 >= n_file) return InvalidLength;
         const uint32_t fa = uint32_t(n - 1);
         const int64_t sstart = int64_t(L.fseq[fa]) + jump;
@@ -2066,116 +2337,34 @@ __device__ __forceinline__ int decode_doc(const DecodeParams &P, const DecodeDes
 
         uint64_t want = alen;
         while (want) {
-            if (!have_op) {
-                if (!qtp.left()) return InvalidLength;
-                uint64_t x;
-                TRY(vq_pop(qtp, x, vs));
-                const bool has_length = x & 1; x >>= 1;
-                const bool diff_nz = x & 1; x >>= 1;
-                const bool is_del = x & 1; x >>= 1;
-                int64_t diff = 0;
-                bool fwd = true;
-                uint64_t l;
-                if (has_length) {
-                    if (is_del) { fwd = x & 1; x >>= 1; }
-                    if (diff_nz) TRY(vq_zigzag(qtp, diff, vs));
-                    l = x;
-                } else {
-                    l = 1;
-                    diff = int64_t(x >> 1) * ((x & 1) ? -1 : 1);
-                }
-                const int64_t raw = int64_t(uint64_t(last_cursor) + uint64_t(diff));
-                int64_t st, raw_end;
-                if (!is_del) { st = raw; raw_end = raw + int64_t(l); }
-                else if (fwd) { st = raw; raw_end = raw; }
-                else { st = raw - int64_t(l); raw_end = raw - int64_t(l); }
-                last_cursor = raw_end;
-                if (l == 0) return ErrCheckout;   // assert!(max_len > 0)
-                op_len = l; op_start = st; op_del = is_del; op_fwd = fwd; have_op = true;
-            }
-            uint64_t take = want < op_len ? want : op_len;
-            CRuns ci = op_del ? del : ins;   // by value: no dynamically indexed private memory
-            bool known = false;
-            Rd cs{0, 0, 0};
-            if (ci.present) {
-                bool has, cknown; uint64_t clen;
-                TRY(cruns_next(C, ci, has, clen, cknown, cs, vs));
-                if (!has) return InvalidLength;
-                if (clen < take) take = clen;
-                if (clen > take) {   // push the remainder back
-                    uint32_t b = 0;
-                    if (cknown) {
-                        uint64_t c2;
-                        walk_chars(C.ptr(cs.s) + cs.p, cs.n, take, ci.ascii, b, c2);
-                    }
-                    ci.pb = 1;
-                    ci.pb_len = clen - take; ci.pb_known = cknown;
-                    ci.pb_s = cknown ? Rd{cs.s, cs.p + b, cs.n - b} : Rd{cs.s, cs.p, 0};
-                    cs.n = b;
-                }
-                known = cknown;
-            }
-            if (op_del) del = ci; else ins = ci;
-            if (!take) return ErrCheckout;
-            // the piece's position; out-of-range positions are left to the host decoder
-            int64_t ppos;
-            bool pfwd = true;
-            if (!op_del) ppos = op_start;
-            else if (op_fwd) ppos = op_start;
-            else { ppos = op_start + int64_t(op_len) - int64_t(take); pfwd = false; }
-            if (ppos < 0 || uint64_t(ppos) >= LIM31) return Defer;
+            if (!op.have) TRY(op.next(qtp, vs));
+            uint64_t take = want < op.len ? want : op.len;
+            bool known;
+            Rd cs;
+            CRuns ci = op.del ? del : ins;
+            TRY(content_take(C, ci, take, known, cs, vs));
+            if (op.del) del = ci; else ins = ci;
+            uint32_t ppos;
+            bool pfwd;
+            TRY(op.piece(take, ppos, pfwd));
             const uint32_t lv = uint32_t(n_lv);
             if (n_lv + take > D.lv_cap) return ErrCapacity;
-            if (!op_del) {   // push_ins
-                if (known) {
-                    // the known pieces tile the insert text in order: the text is copied whole
-                    // once at the end, pieces only place their per-LV offsets
-                    const uint8_t *src = C.ptr(cs.s) + cs.p;
-                    if (ci.ascii) {
-                        for (uint64_t i = lane(); i < take; i += 64) O.cbyte[lv + i] = ins_size + uint32_t(i);
-                    } else {
-                        all_ascii = 0;
-                        uint32_t cnt = 0;
-                        for (uint32_t i = 0; i < cs.n; i += 64) {
-                            const uint32_t j = i + lane();
-                            const bool st = j < cs.n && (src[j] & 0xC0u) != 0x80u;
-                            const uint64_t m = ballot(st);
-                            if (st) O.cbyte[lv + cnt + popc(m & lt_mask())] = ins_size + j;
-                            cnt += popc(m);
-                        }
-                    }
-                    ins_size += cs.n;
-                } else {
-                    fill_cbyte(lv, take, 0xFFFFFFFFu);
-                    complete = 0;
-                }
-                n_lv += take;
-                if (cr_valid && cr_kind == 0 && cr_lv + cr_len == lv && uint64_t(cr_pos) + cr_len == uint64_t(ppos)) {
-                    cr_len += uint32_t(take);
-                } else {
-                    TRY(flush_op());
-                    cr_valid = 1; cr_lv = lv; cr_len = uint32_t(take); cr_pos = uint32_t(ppos); cr_kind = 0; cr_fwd = 1;
-                }
-                op_start += int64_t(take);
-            } else {         // push_del
-                fill_cbyte(lv, take, 0xFFFFFFFFu);
-                n_lv += take;
-                const uint32_t pos = uint32_t(ppos), ln = uint32_t(take);
-                bool merged = false;
-                if (cr_valid && cr_kind == 1 && cr_lv + cr_len == lv) {
-                    if ((cr_len == 1 || cr_fwd) && (ln == 1 || pfwd) && pos == cr_pos) {
-                        cr_len += ln; cr_fwd = 1; merged = true;
-                    } else if ((cr_len == 1 || !cr_fwd) && (ln == 1 || !pfwd) && uint64_t(pos) + ln == cr_pos) {
-                        cr_pos = pos; cr_len += ln; cr_fwd = 0; merged = true;
-                    }
-                }
-                if (!merged) {
-                    TRY(flush_op());
-                    cr_valid = 1; cr_lv = lv; cr_len = ln; cr_pos = pos; cr_kind = 1; cr_fwd = pfwd ? 1 : 0;
-                }
+            if (!op.del && known) {
+                // the known pieces tile the insert text in order: the text is copied whole once
+                // at the end, pieces only place their per-LV offsets
+                place_offsets(O.cbyte, lv, take, C.ptr(cs.s) + cs.p, cs.n, ins_size, ins.ascii);
+                if (!ins.ascii) all_ascii = 0;
+                ins_size += cs.n;
+            } else {
+                place_unknown(O.cbyte, lv, take);
+                if (!op.del) complete = 0;
             }
-            op_len -= take;
-            if (!op_len) have_op = false;
+            n_lv += take;
+            if (!(op.del ? cr.push_del(lv, uint32_t(take), ppos, pfwd) : cr.push_ins(lv, uint32_t(take), ppos))) {
+                TRY(flush_op());
+                cr.start(lv, uint32_t(take), ppos, op.del, pfwd);
+            }
+            op.consume(take);
             want -= take;
         }
     }
@@ -2280,27 +2469,8 @@ __device__ __forceinline__ int decode_doc(const DecodeParams &P, const DecodeDes
     if (lane() == 0) O.poff[n_ent] = n_par;
     prof_mark(4);
     if (pc.n) return InvalidLength;
-    if (ins.present) {   // the content iterators must be exhausted
-        bool has, kn; uint64_t l; Rd s;
-        const int e = cruns_next(C, ins, has, l, kn, s, vs);
-        if (e || has) return InvalidContent;
-    }
-    if (del.present) {
-        bool has, kn; uint64_t l; Rd s;
-        const int e = cruns_next(C, del, has, l, kn, s, vs);
-        if (e || has) return InvalidContent;
-    }
-    {   // CRC (decode_oplog.rs:940-955)
-        const uint32_t reader_len = r.n;
-        bool found; Rd c;
-        TRY(C.chunk_if(r, 100, found, c));
-        if (found && !D.ignore_crc) {
-            if (c.n < 4) return UnexpectedEOF;
-            const uint32_t want = C.byte(0, c.p) | (C.byte(0, c.p + 1) << 8) | (C.byte(0, c.p + 2) << 16) |
-                                  (C.byte(0, c.p + 3) << 24);
-            if (crc32c_par(C.in, len - reader_len, L.crc, P.x2n) != want) return ChecksumFailed;
-        }
-    }
+    TRY(content_done(C, ins, del, vs));
+    TRY(crc_check(C, r, len, D.ignore_crc, L.crc, P.x2n));
     fence_workgroup();
     prof_mark(5);
 
@@ -2333,55 +2503,10 @@ __device__ __forceinline__ int decode_doc(const DecodeParams &P, const DecodeDes
     }
 
     // ---- split op runs at graph-entry boundaries (HostOpLog::finish) --------------------------
-    // one run per lane: its first entry by bisection, its pieces (one per entry it touches) at a
-    // prefix-sum offset; a run rarely spans entries, so the per-lane loops are short
     fence_workgroup();   // the entries were written by lane 0 above
     {
-        uint32_t nout = 0, ebase = 0;   // ebase: the entry of the previous chunk's last run
-        for (uint32_t b0 = 0; b0 < n_pre; b0 += 64) {
-            const uint32_t i = b0 + lane();
-            const bool live = i < n_pre;
-            const uint4 q = live ? O.pre[i] : make_uint4(0, 0, 0, 0);
-            // runs and entries are both in LV order, so a run's first entry is at or after ebase:
-            // search the 64 entries from there in registers, HBM only past that window
-            const uint32_t we = ebase + lane() < n_ent ? O.ent[ebase + lane()].y : 0xFFFFFFFFu;
-            uint32_t c = 0;
-#pragma unroll
-            for (uint32_t st = 32; st >= 1; st >>= 1)
-                if (uint32_t(__shfl(int(we), int(c + st - 1))) <= q.x) c += st;
-            if (c == 63 && rdl(we, 63) <= q.x) c = 64;
-            uint32_t lo = ebase + c, hi = live && c == 64 ? n_ent : lo;
-            while (lo < hi) {
-                const uint32_t m = (lo + hi) >> 1;
-                if (O.ent[m].y <= q.x) lo = m + 1; else hi = m;
-            }
-            uint32_t npc = 0;
-            if (live) {
-                npc = 1;
-                const uint32_t end = q.x + q.y;
-                for (uint32_t e = lo; e < n_ent && O.ent[e].y < end; e++) npc++;
-            }
-            const uint32_t incl = scan_incl(npc);
-            const uint32_t tot = rdl(incl, 63);
-            if (uint64_t(nout) + tot > D.op_cap) return ErrCapacity;
-            if (live) {
-                uint32_t rlv = q.x, rlen = q.y, rpos = q.z, e = lo, k = nout + incl - npc;
-                const uint32_t kf = q.w, kind = kf & 1u, fwd = kf >> 1;
-                while (rlen) {
-                    const uint32_t cut = e < n_ent ? O.ent[e].y : rlv + rlen;
-                    const uint32_t mm = rlen < cut - rlv ? rlen : cut - rlv;
-                    uint32_t apos = rpos;
-                    if (kind == 0) rpos += mm;
-                    else if (!fwd) apos = rpos + rlen - mm;
-                    O.ops[k++] = make_uint4(rlv, mm, apos, kf);
-                    rlv += mm;
-                    rlen -= mm;
-                    if (rlv >= cut) e++;
-                }
-            }
-            nout += tot;
-            ebase = rdl(lo, min(n_pre - 1 - b0, 63u));
-        }
+        uint32_t nout;
+        TRY(split_at_entries(O.pre, n_pre, O.ent, n_ent, O.ops, 0u, D.op_cap, nout));
         R.n_ops = nout;
     }
     prof_mark(6);
@@ -2423,21 +2548,11 @@ __global__ __launch_bounds__(64 * DTGPU_LZ_WAVES) void lz4_kernel(DecodeParams P
     const uint32_t len = D.in_len;
     uint32_t verdict = 0;
     do {   // both waves read the header alike (wave-uniform), so they agree on what follows
-        if (len < 8) break;
-        bool bad = false;
-        const char *magic = "DMNDTYPS";
-        for (uint32_t i = 0; i < 8; i++)
-            if (C.byte(0, i) != uint32_t(uint8_t(magic[i]))) bad = true;
-        if (bad) break;
-        Rd r{0, 8, len - 8};
-        uint64_t pv;
-        if (C.u64v(r, pv) || pv != 0) break;
+        Rd r, c;
+        if (file_open(C, len, r)) break;
         bool found;
-        Rd c;
-        if (C.chunk_if(r, 5, found, c) || !found) break;
         uint64_t ulen;
-        if (C.u64v(c, ulen)) break;
-        if (ulen > (uint64_t(1) << 34) || ulen > 255ull * c.n + 64 || ulen > D.lz_cap) break;
+        if (lz4_chunk(C, r, found, c, ulen) || !found || ulen > D.lz_cap) break;
         if (DTGPU_LZ_WAVES == 3) {   // waves 1 and 2 each: start map (256) + ring; then the slots
             const bool ok = lz4_block<true, true>(C, c, C.lz, uint32_t(ulen), reinterpret_cast<uint4 *>(lds),
                                                   lds + 256, LZ_PRE_RING, nullptr, lds + 2 * (256 + LZ_PRE_RING));
@@ -2505,26 +2620,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DTGPU_DECODE
     const DecodeDesc D = P.docs[doc];
     Lds L;
     const uint32_t F = P.max_file_agents;
-    L.crc = lds;
-    L.fr = lds + 256;
-    L.vq = lds + 320;
-    L.fmap = lds + 512;
-    L.fseq = L.fmap + F;
-    L.noff = L.fseq + F;
+    L.noff = lds_common(L, lds, F);
     L.nlen = L.noff + F;
     L.acnt = L.nlen + F;
     L.aoff = L.acnt + F;
     L.acur = L.aoff + F;
     L.amono = L.acur + F;
     L.lzr = L.amono + F;
-    if (!SIZE) {
-        for (uint32_t i = lane(); i < 256; i += 64) {
-            uint32_t c = i;
-            for (int k = 0; k < 8; k++) c = (c & 1u) ? (c >> 1) ^ CRC_POLY : c >> 1;
-            L.crc[i] = c;
-        }
-        __syncthreads();
-    }
+    if (!SIZE) crc_table(L.crc);
     DecodeResult R{};
     int st = S_OK;
     if (D.skip) st = Defer;
@@ -2537,8 +2640,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DTGPU_DECODE
 // =============================================================================================
 // decode_and_add (ListOpLog::decode_and_add_opts, decode_oplog.rs:476-583; decode_internal's
 // overlap filter :670-913).  One wavefront per (resident oplog, patch) pair; the parse is the
-// decoder's exact path (wave-uniform, varint queues), each step restating dt_host.cpp decode_into
-// so the error order is the host's.  The resident arrays are copied to the merged arenas first
+// decoder's exact path (wave-uniform, varint queues) through the file walk steps shared with
+// decode_doc, in the order of dt_host.cpp decode_into, so the error order is the host's.  add_doc
+// owns the merged agents and the doc id, StartBranch resolution, the overlap filter with its
+// version map, the parents loop and the unwind.  The resident arrays are copied to the merged arenas first
 // (lane-parallel); agent runs, op runs, entries and the frontier then grow with the reference's
 // RLE rules, so the merged arrays equal the host decode_and_add's element for element.
 // =============================================================================================
@@ -2609,11 +2714,9 @@ __device__ __forceinline__ int add_doc(const AddParams &P, const AddDesc &D, Dec
     uint32_t la_lv = 0, la_len = 0, la_agent = 0xFFFFFFFFu, la_seq = 0;    // last agent run
     if (n_aruns) { const uint4 a = M.aruns[n_aruns - 1]; la_lv = a.x; la_len = a.y; la_agent = a.z; la_seq = a.w; }
     uint32_t last_end = n_ent ? M.ent[n_ent - 1].y : 0u;                 // last graph entry's end
-    uint32_t cr_valid = 0, cr_lv = 0, cr_len = 0, cr_pos = 0, cr_kind = 0, cr_fwd = 0;   // pending op run
-    if (D.b_n_ops) {
-        const uint4 o = M.ops[D.b_n_ops - 1];
-        cr_valid = 1; cr_lv = o.x; cr_len = o.y; cr_pos = o.z; cr_kind = o.w & 1u; cr_fwd = (o.w >> 1) & 1u;
-    }
+    OpRun cr;   // pending op run: the resident's last, which the file's first piece may extend
+    cr.init();
+    if (D.b_n_ops) cr.load(M.ops[D.b_n_ops - 1]);
     uint32_t n_pre = 0, n_vm = 0;
     uint32_t vm_file = 0, vm_local = 0, vm_len = 0;   // last version-map run (file offset from new_op_start)
     bool dirty = false;   // lane-0 stores the next lane-parallel scan must see (fenced lazily)
@@ -2716,11 +2819,11 @@ __device__ __forceinline__ int add_doc(const AddParams &P, const AddDesc &D, Dec
         return true;
     };
     auto flush_op = [&]() -> int {
-        if (!cr_valid) return S_OK;
+        if (!cr.valid) return S_OK;
         if (n_pre >= D.c_pre) return int(ErrCapacity);
-        if (lane() == 0) M.pre[n_pre] = make_uint4(cr_lv, cr_len, cr_pos, cr_kind | (cr_fwd << 1));
+        if (lane() == 0) M.pre[n_pre] = cr.quad();
         n_pre++;
-        cr_valid = 0;
+        cr.valid = 0;
         return S_OK;
     };
 
@@ -2757,26 +2860,15 @@ __device__ __forceinline__ int add_doc(const AddParams &P, const AddDesc &D, Dec
     __syncthreads();
 
     // ---- header, LZ4 --------------------------------------------------------------------------
-    if (len < 8) return UnexpectedEOF;
-    {
-        const char *magic = "DMNDTYPS";
-        for (uint32_t i = 0; i < 8; i++)
-            if (C.byte(0, i) != uint32_t(uint8_t(magic[i]))) return InvalidMagic;
-    }
-    Rd r{0, 8, len - 8};
-    uint64_t pv;
-    TRY(C.u64v(r, pv));
-    if (pv != 0) return UnsupportedProtocolVersion;
+    Rd r;
+    TRY(file_open(C, len, r));
     Rd comp{SRC_LZ, 0, 0};
     bool has_comp = false;
     {
         bool found; Rd c;
-        TRY(C.chunk_if(r, 5, found, c));
+        uint64_t ulen;
+        TRY(lz4_chunk(C, r, found, c, ulen));
         if (found) {
-            uint64_t ulen;
-            TRY(C.u64v(c, ulen));
-            if (ulen > (uint64_t(1) << 34)) return LZ4DecompressionError;
-            if (ulen > 255ull * c.n + 64) return LZ4DecompressionError;
             if (ulen > D.lz_cap) return ErrCapacity;
             if (!lz4_block(C, c, C.lz, uint32_t(ulen), reinterpret_cast<uint4 *>(L.fr), nullptr, 0u)) return LZ4DecompressionError;
             comp.n = uint32_t(ulen);
@@ -2880,29 +2972,10 @@ __device__ __forceinline__ int add_doc(const AddParams &P, const AddDesc &D, Dec
         }
     }
     Rd pc;
-    TRY(C.expect_chunk(r, 20, pc));
     CRuns ins{}, del{};
-    for (;;) {
-        bool found; Rd ch;
-        TRY(C.chunk_if(pc, 24, found, ch));
-        if (!found) break;
-        uint64_t tag;
-        TRY(C.u32v(ch, tag));
-        if (tag > 1) return InvalidContent;
-        CRuns it{};
-        it.present = 1;
-        TRY(content_str<false>(C, ch, comp, has_comp, it.text, it.ascii));
-        Rd runs;
-        TRY(C.expect_chunk(ch, 25, runs));
-        it.runs = vq_make(C.in, runs);
-        it.t0 = it.text.p;
-        if (tag == 0) ins = it; else del = it;
-    }
-    Rd av, tp, hist;
-    TRY(C.expect_chunk(pc, 21, av));
-    TRY(C.expect_chunk(pc, 22, tp));
-    TRY(C.expect_chunk(pc, 23, hist));
-    VQ qav = vq_make(C.in, av), qtp = vq_make(C.in, tp), qhist = vq_make(C.in, hist);
+    uint32_t cik_bytes;
+    VQ qav, qtp, qhist;
+    TRY(patch_chunks<false>(C, r, comp, has_comp, pc, ins, del, cik_bytes, qav, qtp, qhist));
 
     // The file continues the resident version, or its operations are filtered against what the
     // oplog already has (patches_overlap, decode_oplog.rs:670; file times go underwater).
@@ -2912,19 +2985,12 @@ __device__ __forceinline__ int add_doc(const AddParams &P, const AddDesc &D, Dec
     uint64_t next_assign = first_new, next_file = new_op_start;
 
     // ---- OpVersions + OpTypeAndPosition + content runs (decode_oplog.rs:29-68, 731-850) -------
-    int64_t last_cursor = 0;
-    bool have_op = false;
-    uint64_t op_len = 0;
-    int64_t op_start = 0;
-    bool op_del = false, op_fwd = true;
+    FileOp op;
+    op.init();
     while (qav.left()) {
         uint64_t n, alen;
-        int64_t jump = 0;
-        TRY(vq_pop(qav, n, vs));
-        const bool has_jump = n & 1;
-        n >>= 1;
-        TRY(vq_pop(qav, alen, vs));
-        if (has_jump) TRY(vq_zigzag(qav, jump, vs));
+        int64_t jump;
+        TRY(arun_next(qav, vs, n, alen, jump));
         if (n == 0 || n - 1 >= n_file) return InvalidLength;
         const uint32_t fa = uint32_t(n - 1);
         const uint32_t agent = L.fmap[fa];
@@ -2956,120 +3022,40 @@ __device__ __forceinline__ int add_doc(const AddParams &P, const AddDesc &D, Dec
 
             uint64_t want = l;   // parse_next_patches (decode_oplog.rs:731-778)
             while (want) {
-                if (!have_op) {
-                    if (!qtp.left()) return InvalidLength;
-                    uint64_t x;
-                    TRY(vq_pop(qtp, x, vs));
-                    const bool has_length = x & 1; x >>= 1;
-                    const bool diff_nz = x & 1; x >>= 1;
-                    const bool is_del = x & 1; x >>= 1;
-                    int64_t diff = 0;
-                    bool fwd = true;
-                    uint64_t ol;
-                    if (has_length) {
-                        if (is_del) { fwd = x & 1; x >>= 1; }
-                        if (diff_nz) TRY(vq_zigzag(qtp, diff, vs));
-                        ol = x;
-                    } else {
-                        ol = 1;
-                        diff = int64_t(x >> 1) * ((x & 1) ? -1 : 1);
-                    }
-                    const int64_t raw = int64_t(uint64_t(last_cursor) + uint64_t(diff));
-                    int64_t st, raw_end;
-                    if (!is_del) { st = raw; raw_end = raw + int64_t(ol); }
-                    else if (fwd) { st = raw; raw_end = raw; }
-                    else { st = raw - int64_t(ol); raw_end = raw - int64_t(ol); }
-                    last_cursor = raw_end;
-                    if (ol == 0) return ErrCheckout;   // assert!(max_len > 0)
-                    op_len = ol; op_start = st; op_del = is_del; op_fwd = fwd; have_op = true;
-                }
-                uint64_t take = want < op_len ? want : op_len;
-                CRuns ci = op_del ? del : ins;
-                bool known = false;
-                Rd cs{0, 0, 0};
-                if (ci.present) {
-                    bool has, cknown; uint64_t clen;
-                    TRY(cruns_next(C, ci, has, clen, cknown, cs, vs));
-                    if (!has) return InvalidLength;
-                    if (clen < take) take = clen;
-                    if (clen > take) {   // push the remainder back (SplitableSpan truncate)
-                        uint32_t b = 0;
-                        if (cknown) {
-                            uint64_t c2;
-                            walk_chars(C.ptr(cs.s) + cs.p, cs.n, take, ci.ascii, b, c2);
-                        }
-                        ci.pb = 1;
-                        ci.pb_len = clen - take; ci.pb_known = cknown;
-                        ci.pb_s = cknown ? Rd{cs.s, cs.p + b, cs.n - b} : Rd{cs.s, cs.p, 0};
-                        cs.n = b;
-                    }
-                    known = cknown;
-                }
-                if (op_del) del = ci; else ins = ci;
-                if (!take) return ErrCheckout;
+                if (!op.have) TRY(op.next(qtp, vs));
+                uint64_t take = want < op.len ? want : op.len;
+                bool known;
+                Rd cs;
+                CRuns ci = op.del ? del : ins;
+                TRY(content_take(C, ci, take, known, cs, vs));
+                if (op.del) del = ci; else ins = ci;
                 if (keep) {
-                    int64_t ppos;
-                    bool pfwd = true;
-                    if (!op_del) ppos = op_start;
-                    else if (op_fwd) ppos = op_start;
-                    else { ppos = op_start + int64_t(op_len) - int64_t(take); pfwd = false; }
-                    if (ppos < 0 || uint64_t(ppos) >= LIM31) return Defer;
+                    uint32_t ppos;
+                    bool pfwd;
+                    TRY(op.piece(take, ppos, pfwd));
                     const uint32_t lv = uint32_t(n_lv);
                     if (n_lv + take > D.c_lv) return ErrCapacity;
-                    if (!op_del) {   // push_ins
-                        if (known) {
-                            if (n_content + cs.n > D.c_content) return ErrCapacity;
-                            const uint8_t *src = C.ptr(cs.s) + cs.p;
-                            // a catch-up patch keeps every piece: the known pieces tile the insert
-                            // text in order, copied whole at the end
-                            if (overlap)
-                                for (uint32_t i = lane(); i < cs.n; i += 64) M.content[n_content + i] = src[i];
-                            if (ci.ascii) {
-                                for (uint64_t i = lane(); i < take; i += 64) M.cbyte[lv + i] = n_content + uint32_t(i);
-                            } else {
-                                all_ascii = 0;
-                                uint32_t cnt = 0;
-                                for (uint32_t i = 0; i < cs.n; i += 64) {
-                                    const uint32_t j = i + lane();
-                                    const bool s0 = j < cs.n && (src[j] & 0xC0u) != 0x80u;
-                                    const uint64_t m = ballot(s0);
-                                    if (s0) M.cbyte[lv + cnt + popc(m & lt_mask())] = n_content + j;
-                                    cnt += popc(m);
-                                }
-                            }
-                            n_content += cs.n;
-                        } else {
-                            for (uint64_t i = lane(); i < take; i += 64) M.cbyte[lv + i] = 0xFFFFFFFFu;
-                            complete = 0;
-                        }
-                        n_lv += take;
-                        if (cr_valid && cr_kind == 0 && cr_lv + cr_len == lv && uint64_t(cr_pos) + cr_len == uint64_t(ppos)) {
-                            cr_len += uint32_t(take);
-                        } else {
-                            TRY(flush_op());
-                            cr_valid = 1; cr_lv = lv; cr_len = uint32_t(take); cr_pos = uint32_t(ppos); cr_kind = 0; cr_fwd = 1;
-                        }
-                    } else {         // push_del
-                        for (uint64_t i = lane(); i < take; i += 64) M.cbyte[lv + i] = 0xFFFFFFFFu;
-                        n_lv += take;
-                        const uint32_t pos = uint32_t(ppos), ln = uint32_t(take);
-                        bool merged = false;
-                        if (cr_valid && cr_kind == 1 && cr_lv + cr_len == lv) {
-                            if ((cr_len == 1 || cr_fwd) && (ln == 1 || pfwd) && pos == cr_pos) {
-                                cr_len += ln; cr_fwd = 1; merged = true;
-                            } else if ((cr_len == 1 || !cr_fwd) && (ln == 1 || !pfwd) && uint64_t(pos) + ln == cr_pos) {
-                                cr_pos = pos; cr_len += ln; cr_fwd = 0; merged = true;
-                            }
-                        }
-                        if (!merged) {
-                            TRY(flush_op());
-                            cr_valid = 1; cr_lv = lv; cr_len = ln; cr_pos = pos; cr_kind = 1; cr_fwd = pfwd ? 1 : 0;
-                        }
+                    if (!op.del && known) {
+                        if (n_content + cs.n > D.c_content) return ErrCapacity;
+                        const uint8_t *src = C.ptr(cs.s) + cs.p;
+                        // a catch-up patch keeps every piece: the known pieces tile the insert
+                        // text in order, copied whole at the end
+                        if (overlap)
+                            for (uint32_t i = lane(); i < cs.n; i += 64) M.content[n_content + i] = src[i];
+                        place_offsets(M.cbyte, lv, take, src, cs.n, n_content, ins.ascii);
+                        if (!ins.ascii) all_ascii = 0;
+                        n_content += cs.n;
+                    } else {
+                        place_unknown(M.cbyte, lv, take);
+                        if (!op.del) complete = 0;
+                    }
+                    n_lv += take;
+                    if (!(op.del ? cr.push_del(lv, uint32_t(take), ppos, pfwd) : cr.push_ins(lv, uint32_t(take), ppos))) {
+                        TRY(flush_op());
+                        cr.start(lv, uint32_t(take), ppos, op.del, pfwd);
                     }
                 }
-                if (!op_del) op_start += int64_t(take);
-                op_len -= take;
-                if (!op_len) have_op = false;
+                op.consume(take);
                 want -= take;
             }
         }
@@ -3169,68 +3155,14 @@ __device__ __forceinline__ int add_doc(const AddParams &P, const AddDesc &D, Dec
     }
     if (next_file != file_end || next_hist != next_assign) return InvalidLength;
     if (pc.n) return InvalidLength;
-    if (ins.present) {
-        bool has, kn; uint64_t l; Rd s;
-        const int e = cruns_next(C, ins, has, l, kn, s, vs);
-        if (e || has) return InvalidContent;
-    }
-    if (del.present) {
-        bool has, kn; uint64_t l; Rd s;
-        const int e = cruns_next(C, del, has, l, kn, s, vs);
-        if (e || has) return InvalidContent;
-    }
-    {   // CRC (decode_oplog.rs:940-955)
-        const uint32_t reader_len = r.n;
-        bool found; Rd c;
-        TRY(C.chunk_if(r, 100, found, c));
-        if (found && !D.ignore_crc) {
-            if (c.n < 4) return UnexpectedEOF;
-            const uint32_t want = C.byte(0, c.p) | (C.byte(0, c.p + 1) << 8) | (C.byte(0, c.p + 2) << 16) |
-                                  (C.byte(0, c.p + 3) << 24);
-            if (crc32c_par(C.in, len - reader_len, L.crc, P.x2n) != want) return ChecksumFailed;
-        }
-    }
+    TRY(content_done(C, ins, del, vs));
+    TRY(crc_check(C, r, len, D.ignore_crc, L.crc, P.x2n));
     fence_workgroup();
 
     // ---- HostOpLog::finish: the new op runs (and the resident's last) split at entry ends ------
     {
-        const uint32_t o0 = D.b_n_ops ? D.b_n_ops - 1 : 0;
-        uint32_t nout = o0;
-        for (uint32_t b0 = 0; b0 < n_pre; b0 += 64) {
-            const uint32_t i = b0 + lane();
-            const bool live = i < n_pre;
-            const uint4 q = live ? M.pre[i] : make_uint4(0, 0, 0, 0);
-            uint32_t lo = 0, hi = live ? n_ent : 0;   // first entry ending above the run's first LV
-            while (lo < hi) {
-                const uint32_t m = (lo + hi) >> 1;
-                if (M.ent[m].y <= q.x) lo = m + 1; else hi = m;
-            }
-            uint32_t npc = 0;
-            if (live) {
-                npc = 1;
-                const uint32_t end = q.x + q.y;
-                for (uint32_t e = lo; e < n_ent && M.ent[e].y < end; e++) npc++;
-            }
-            const uint32_t incl = scan_incl(npc);
-            const uint32_t tot = rdl(incl, 63);
-            if (uint64_t(nout) + tot > D.c_op) return ErrCapacity;
-            if (live) {
-                uint32_t rlv = q.x, rlen = q.y, rpos = q.z, e = lo, k = nout + incl - npc;
-                const uint32_t kf = q.w, kind = kf & 1u, fwd = kf >> 1;
-                while (rlen) {
-                    const uint32_t cut = e < n_ent ? M.ent[e].y : rlv + rlen;
-                    const uint32_t mm = rlen < cut - rlv ? rlen : cut - rlv;
-                    uint32_t apos = rpos;
-                    if (kind == 0) rpos += mm;
-                    else if (!fwd) apos = rpos + rlen - mm;
-                    M.ops[k++] = make_uint4(rlv, mm, apos, kf);
-                    rlv += mm;
-                    rlen -= mm;
-                    if (rlv >= cut) e++;
-                }
-            }
-            nout += tot;
-        }
+        uint32_t nout;
+        TRY(split_at_entries(M.pre, n_pre, M.ent, n_ent, M.ops, D.b_n_ops ? D.b_n_ops - 1 : 0u, D.c_op, nout));
         R.n_ops = n_pre ? nout : D.b_n_ops;
     }
     if (lane() == 0) M.poff[n_ent] = n_par;
@@ -3277,7 +3209,7 @@ __device__ __forceinline__ void add_copy_base(const AddParams &P, const AddDesc 
 }
 
 #ifndef DTGPU_ADD_WAVES
-#define DTGPU_ADD_WAVES 2   // 231 VGPRs, no VGPR spills (4: 218 spilled, 1.5x slower)
+#define DTGPU_ADD_WAVES 2   // 227 VGPRs, no VGPR spills (4: 218 spilled, 1.5x slower)
 #endif
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DTGPU_ADD_WAVES))) void decode_add_kernel(AddParams P) {
     extern __shared__ uint32_t lds[];
@@ -3286,20 +3218,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DTGPU_ADD_WA
     const AddDesc D = P.docs[doc];
     Lds L{};
     const uint32_t F = P.max_file_agents;
-    L.crc = lds;
-    L.fr = lds + 256;
-    L.vq = lds + 320;
-    L.fmap = lds + 512;
-    L.fseq = L.fmap + F;
-    L.acnt = L.fseq + F;            // per merged agent: seq end,
+    L.acnt = lds_common(L, lds, F);    // per merged agent: seq end,
     L.amono = L.acnt + P.max_agents;   // runs increase,
     L.acur = L.amono + P.max_agents;   // last hit
-    for (uint32_t i = lane(); i < 256; i += 64) {
-        uint32_t c = i;
-        for (int k = 0; k < 8; k++) c = (c & 1u) ? (c >> 1) ^ CRC_POLY : c >> 1;
-        L.crc[i] = c;
-    }
-    __syncthreads();
+    crc_table(L.crc);
     Merged M;
     M.in = P.m_in + D.m_in;
     M.content = P.m_content + D.m_content;

@@ -52,6 +52,12 @@ uint32_t multmodp_host(uint32_t a, uint32_t b) {
     return p;
 }
 
+// x^(2^k) mod the CRC-32C polynomial, k < 32: the table the kernels' CRC segment combine reads
+void crc_x2n(uint32_t (&x2n)[32]) {
+    x2n[0] = 1u << 30;
+    for (int k = 1; k < 32; k++) x2n[k] = multmodp_host(x2n[k - 1], x2n[k - 1]);
+}
+
 uint64_t align256(uint64_t x) { return (x + 255) & ~uint64_t(255); }
 
 // SoA bytes of one decoded document: 16 B per op run and agent run, 8 per entry (+4 per CSR slot),
@@ -179,8 +185,7 @@ dtgpu_status dtgpu_decode_create(const uint8_t *const *docs, const size_t *lens,
     P.docs = D->d_desc.p;
     P.results = D->d_res.p;
     P.n_docs = uint32_t(n);
-    P.x2n[0] = 1u << 30;
-    for (int k = 1; k < 32; k++) P.x2n[k] = multmodp_host(P.x2n[k - 1], P.x2n[k - 1]);
+    crc_x2n(P.x2n);
     // sizing pass
     P.size_only = 1;
     P.max_file_agents = 0;
@@ -478,8 +483,7 @@ dtgpu_status dtgpu_decode_add(const dtgpu_decoded *B, const uint8_t *const *patc
     A.m_aruns = M->aruns.p; A.m_ops = M->ops.p; A.m_ent = M->ent.p; A.m_poff = M->poff.p; A.m_par = M->par.p;
     A.m_cbyte = M->cbyte.p; A.m_agents = M->agents.p; A.m_ver = M->ver.p; A.m_ffr = M->ffr.p; A.scr = d_scr.p;
     A.docs = d_ad.p; A.results = M->d_res.p; A.n_docs = uint32_t(n); A.max_file_agents = max_f; A.max_agents = max_a;
-    A.x2n[0] = 1u << 30;
-    for (int k = 1; k < 32; k++) A.x2n[k] = multmodp_host(A.x2n[k - 1], A.x2n[k - 1]);
+    crc_x2n(A.x2n);
     CK(hipEventRecord(M->ev0, s));
     if (launch_decode_add(A, s)) return DTGPU_ERR_HIP;
     CK(hipEventRecord(M->ev1, s));
@@ -752,8 +756,7 @@ dtgpu_status dtgpu_decode_encode_from(const dtgpu_decoded *B, const uint32_t *do
     P.counts = d_cnt.p; P.results = d_res.p; P.n_docs = uint32_t(n); P.lds_entries = lds_entries;
     P.prof = getenv("DTGPU_PATCH_PROF") ? 1u : 0u;   // read at call time: the build waves count their phase cycles
     P.flags = flags & (DTGPU_ENCODE_STORE_INSERTED_CONTENT | DTGPU_ENCODE_COMPRESS_CONTENT);
-    P.x2n[0] = 1u << 30;
-    for (int k = 1; k < 32; k++) P.x2n[k] = multmodp_host(P.x2n[k - 1], P.x2n[k - 1]);
+    crc_x2n(P.x2n);
     CK(hipEventRecord(own.e[0], s));
     if (launch_patch_mark(P, s)) return DTGPU_ERR_HIP;
     CK(hipEventRecord(own.e[1], s));

@@ -139,6 +139,12 @@ def encode_dt(agent_names, ops, del_content_unknown=False, ins_runs_per_op=False
     return bytes(out)
 
 
+def unicode_ops(ops):
+    """The op list with every insert's ASCII text mapped to 2- and 3-byte characters."""
+    g = lambda t: "".join(chr(0x3B1 + ord(c) - 97) if i % 2 else chr(0x4E00 + ord(c)) for i, c in enumerate(t))
+    return [(a, k, p, n, g(t) if k == 0 else t, par) for a, k, p, n, t, par in ops]
+
+
 def graph_docs():
     """Documents whose histories stress the OpParents decode: merges of up to 12 parents in
     arbitrary order (duplicates included), foreign (agent, seq) parents, runs of single-parent

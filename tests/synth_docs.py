@@ -2,6 +2,7 @@
 import random
 
 import dt_amd
+from dt_encode import encode_dt, unicode_ops
 
 
 def phased_doc(seed, phases=14):
@@ -45,3 +46,26 @@ def phased_doc(seed, phases=14):
                 o.add_insert(a, rng.randint(0, length), t)
                 length += len(t)
     return o.encode()
+
+
+def content_shape_specs():
+    """(agent names, op list, encode_dt flags) of 13 documents that exercise the decoder's
+    content-run handling: ASCII text in one known run, Unicode text, one ContentIsKnown run per
+    insert, deleted content (unknown), and last a document with unknown insert content (which the
+    reference cannot check out).  A prefix of an op list encodes, with the same flags, to a
+    valid document that the whole one extends."""
+    out = []
+    for doc in range(12):
+        na, ops = dt_amd.synth_ops(doc, 2000)
+        kind = doc % 4
+        if kind == 1:
+            ops = unicode_ops(ops)
+        out.append(([f"a{i}" for i in range(na)], ops,
+                    {"ins_runs_per_op": kind == 2, "del_content_unknown": kind == 3}))
+    na, ops = dt_amd.synth_ops(99, 1000)
+    out.append(([f"a{i}" for i in range(na)], ops, {"unknown_every": 7}))
+    return out
+
+
+def content_shape_docs():
+    return [encode_dt(names, ops, **flags) for names, ops, flags in content_shape_specs()]

@@ -4,16 +4,11 @@ import numpy as np
 import pytest
 
 import dt_amd
-from dt_encode import encode_dt
+from dt_encode import encode_dt, unicode_ops as _unicode
 from oracle.oracle import OpLog as OracleOpLog
 
 WHAT = ["ops", "agent_runs", "entries", "parent_offsets", "parents", "content", "char_offsets", "version",
         "agent_names"]
-
-
-def _unicode(ops):
-    g = lambda t: "".join(chr(0x3B1 + ord(c) - 97) if i % 2 else chr(0x4E00 + ord(c)) for i, c in enumerate(t))
-    return [(a, k, p, n, g(t) if k == 0 else t, par) for a, k, p, n, t, par in ops]
 
 
 def _builder(n_agents, ops):

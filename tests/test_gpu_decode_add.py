@@ -12,7 +12,9 @@ import numpy as np
 import pytest
 
 import golden_data as G
+from dt_encode import encode_dt, unicode_ops
 from oracle.oracle import OpLog as OracleOpLog
+from synth_docs import content_shape_specs
 from test_encoder import VECTORS
 import dt_amd
 
@@ -261,3 +263,63 @@ def test_random_split_merges_in_random_order():
         pairs.append((full.history(a).encode(), full.history(b).encode()))
     _, sts = _check_batch(pairs)
     assert all(s == 0 for s in sts), sts
+
+
+def _prefix(spec, num, den):
+    """The document of the first num/den of a content-shape spec's op list (same flags)."""
+    names, ops, flags = spec
+    return encode_dt(names, ops[:len(ops) * num // den], **flags)
+
+
+def test_content_shapes_merged_into_prefixes():
+    """The content shapes of synth_docs.content_shape_specs (Unicode text, one ContentIsKnown run
+    per insert, deleted content unknown, unknown insert content) through the add path: each whole
+    file merged into an empty oplog and into the first third and half of its own op list (overlap
+    path), and the patch since the half merged into the half (catch-up path; not for the document
+    with unknown insert content, whose patch the host encoder refuses).  Every pair merges to the
+    whole document, equal to the host's."""
+    pairs, want = [], []
+    for k, spec in enumerate(content_shape_specs()):
+        whole = encode_dt(spec[0], spec[1], **spec[2])
+        n = sum(o[3] for o in spec[1])
+        third, half = _prefix(spec, 1, 3), _prefix(spec, 1, 2)
+        pairs += [(None, whole), (third, whole), (half, whole)]
+        want += [n] * 3
+        if k < 12:
+            v = dt_amd.ListOpLog.load_from(half).local_frontier()
+            pairs.append((half, dt_amd.ListOpLog.load_from(whole).encode_from(v, dt_amd.ENCODE_PATCH)))
+            want.append(n)
+    m, sts = _check_batch(pairs)
+    assert sts == [0] * len(pairs), sts
+    assert [len(m.export(i, "char_offsets")) for i in range(len(pairs))] == want
+
+
+# Pairs the device hands to the host (DECODE_DEFER) per file, measured before the decoder's file
+# walk was shared (the test runs no code of that change): 38, 34, 35 of 548, 479, 655.  An upper
+# bound since.
+_SMALL_SHAPES = [
+    (1, True, {}, 38),
+    (2, False, {"ins_runs_per_op": True}, 34),
+    (3, False, {"del_content_unknown": True}, 35),
+]
+
+
+@pytest.mark.parametrize("doc,uni,flags,max_deferred", _SMALL_SHAPES)
+def test_every_corruption_of_content_shapes_unwinds_like_the_host(doc, uni, flags, max_deferred):
+    """Every single-byte corruption of three small content-shape files (Unicode text; one
+    ContentIsKnown run per insert; deleted content unknown) merged into the first half of the
+    file's own op list: the device status equals the host's and a failed merge leaves the resident
+    arrays as they were (_check_batch)."""
+    na, ops = dt_amd.synth_ops(doc, 80)
+    spec = ([f"a{i}" for i in range(na)], unicode_ops(ops) if uni else ops, flags)
+    enc, base = encode_dt(*spec[:2], **flags), _prefix(spec, 1, 2)
+    pairs = []
+    for i in range(len(enc)):
+        bad = bytearray(enc)
+        bad[i] ^= 0xFF
+        pairs.append((base, bytes(bad)))
+    _, sts = _check_batch(pairs)
+    deferred = sum(1 for s in sts if s == dt_amd.DECODE_DEFER)
+    print(f"content shape {doc}: {len(enc)} bytes, {deferred} deferred, statuses {sorted(set(sts))}")
+    assert sum(1 for s in sts if s not in (0, dt_amd.DECODE_DEFER)) > len(enc) // 2
+    assert deferred <= max_deferred

@@ -4,9 +4,10 @@ unknown content) and the device-staged checkout, against the host decoder and th
 import numpy as np
 import pytest
 
-from dt_encode import encode_dt, graph_docs
+from dt_encode import graph_docs
 from oracle.oracle import OpLog as OracleOpLog
-from test_dt_encode import WHAT, _unicode
+from synth_docs import content_shape_docs as _docs
+from test_dt_encode import WHAT
 
 pytestmark = pytest.mark.gpu
 
@@ -17,20 +18,6 @@ import dt_amd  # noqa: E402
 def _need_gpu():
     if dt_amd.device_count() < 1:
         pytest.fail("no HIP device visible: the engine has no CPU fallback")
-
-
-def _docs():
-    out = []
-    for doc in range(12):
-        na, ops = dt_amd.synth_ops(doc, 2000)
-        names = [f"a{i}" for i in range(na)]
-        kind = doc % 4
-        if kind == 1:
-            ops = _unicode(ops)
-        out.append(encode_dt(names, ops, ins_runs_per_op=(kind == 2), del_content_unknown=(kind == 3)))
-    na, ops = dt_amd.synth_ops(99, 1000)
-    out.append(encode_dt([f"a{i}" for i in range(na)], ops, unknown_every=7))   # checkout: ErrCheckout
-    return out
 
 
 def test_device_decode_matches_host_on_synthetic_dt():
