@@ -22,6 +22,22 @@ pub struct dtgpu_patches {
     _p: [u8; 0],
 }
 #[repr(C)]
+pub struct dtgpu_intersect {
+    _p: [u8; 0],
+}
+/// A batch of version summaries, flattened (include/dtgpu.h `dtgpu_summaries`).
+#[repr(C)]
+pub struct dtgpu_summaries {
+    pub doc: *const u32,
+    pub entry_off: *const usize,
+    pub names: *const u8,
+    pub name_off: *const usize,
+    pub range_off: *const usize,
+    pub ranges: *const u64,
+    pub versions: *const u64,
+    pub version_off: *const usize,
+}
+#[repr(C)]
 #[derive(Default, Clone, Copy, Debug)]
 pub struct dtgpu_doc_result {
     pub status: u32,
@@ -140,6 +156,28 @@ extern "C" {
     pub fn dtgpu_patches_profile(p: *const dtgpu_patches, i: usize, out: *mut u32) -> dtgpu_status;
     pub fn dtgpu_patches_free(p: *mut dtgpu_patches);
     pub fn dtgpu_batch_create_decoded(dec: *mut dtgpu_decoded, out: *mut *mut dtgpu_batch) -> dtgpu_status;
+    // version summaries: what a peer that knows no local LVs holds (src/causalgraph/summary.rs:119-264)
+    pub fn dtgpu_oplog_summarize(oplog: *const dtgpu_oplog, names: *mut u8, names_cap: usize, name_off: *mut usize,
+                                 range_off: *mut usize, entry_cap: usize, ranges: *mut u64, range_cap: usize,
+                                 sizes: *mut usize) -> dtgpu_status;
+    pub fn dtgpu_oplog_intersect_summary(oplog: *const dtgpu_oplog, s: *const dtgpu_summaries, i: usize,
+                                         frontier: *mut u64, frontier_cap: usize, n_frontier: *mut usize,
+                                         triples: *mut u64, triple_cap: usize, n_triples: *mut usize) -> dtgpu_status;
+    pub fn dtgpu_decode_intersect(base: *const dtgpu_decoded, s: *const dtgpu_summaries, n: usize, ms: *mut f32,
+                                  out: *mut *mut dtgpu_intersect) -> dtgpu_status;
+    pub fn dtgpu_intersect_size(x: *const dtgpu_intersect) -> usize;
+    pub fn dtgpu_intersect_result(x: *const dtgpu_intersect, i: usize, frontier: *mut u64, cap: usize,
+                                  n_frontier: *mut usize) -> dtgpu_status;
+    pub fn dtgpu_intersect_remainder(x: *const dtgpu_intersect, i: usize, triples: *mut u64, cap: usize,
+                                     n: *mut usize) -> dtgpu_status;
+    pub fn dtgpu_intersect_profile(x: *const dtgpu_intersect, i: usize, out: *mut u32) -> dtgpu_status;
+    pub fn dtgpu_intersect_free(x: *mut dtgpu_intersect);
+    pub fn dtgpu_decode_encode_from_summaries(base: *const dtgpu_decoded, s: *const dtgpu_summaries, n: usize,
+                                              flags: u32, ms: *mut f32, patches: *mut *mut dtgpu_patches,
+                                              isect: *mut *mut dtgpu_intersect) -> dtgpu_status;
+    pub fn dtgpu_decode_summarize(base: *const dtgpu_decoded, i: usize, names: *mut u8, names_cap: usize,
+                                  name_off: *mut usize, range_off: *mut usize, entry_cap: usize, ranges: *mut u64,
+                                  range_cap: usize, sizes: *mut usize) -> dtgpu_status;
     pub fn dtgpu_device_count() -> c_int;
     // the decoded oplog's arrays (op runs, inserted content, per-LV byte offsets, ...)
     pub fn dtgpu_oplog_export(oplog: *const dtgpu_oplog, what: c_int, out: *mut c_void, cap: usize) -> usize;
@@ -149,6 +187,9 @@ extern "C" {
 pub const DTGPU_EXPORT_OPS: c_int = 0;
 pub const DTGPU_EXPORT_CONTENT: c_int = 5;
 pub const DTGPU_EXPORT_CHAR_OFFSETS: c_int = 6;
+
+/// `VersionSummary` (src/causalgraph/summary.rs:13-30): per agent name, the seq ranges held.
+pub type VersionSummary = Vec<(String, Vec<(u64, u64)>)>;
 
 /// A decoded oplog (`ListOpLog`), owned.
 pub struct ListOpLog {
@@ -253,6 +294,62 @@ impl ListOpLog {
             let mut v = vec![0u64; n as usize];
             dtgpu_oplog_dominators(self.h, a.as_ptr(), a.len(), b.as_ptr(), b.len(), v.as_mut_ptr(), v.len());
             Ok(v)
+        }
+    }
+    /// `AgentAssignment::summarize_versions()` (src/causalgraph/summary.rs:119-132): per agent
+    /// with ops, its name and its seq ranges.
+    pub fn summarize_versions(&self) -> Result<VersionSummary, i32> {
+        unsafe {
+            let mut sizes = [0usize; 3];
+            let null8 = std::ptr::null_mut();
+            let s = dtgpu_oplog_summarize(self.h, null8, 0, std::ptr::null_mut(), std::ptr::null_mut(), 0,
+                                          std::ptr::null_mut(), 0, sizes.as_mut_ptr());
+            if s != DTGPU_OK { return Err(s); }
+            let (ne, nb, nr) = (sizes[0], sizes[1], sizes[2]);
+            let mut names = vec![0u8; nb.max(1)];
+            let (mut name_off, mut range_off) = (vec![0usize; ne + 1], vec![0usize; ne + 1]);
+            let mut ranges = vec![0u64; (2 * nr).max(1)];
+            let s = dtgpu_oplog_summarize(self.h, names.as_mut_ptr(), nb, name_off.as_mut_ptr(), range_off.as_mut_ptr(), ne,
+                                          ranges.as_mut_ptr(), nr, sizes.as_mut_ptr());
+            if s != DTGPU_OK { return Err(s); }
+            Ok((0..ne).map(|e| (String::from_utf8_lossy(&names[name_off[e]..name_off[e + 1]]).into_owned(),
+                                (range_off[e]..range_off[e + 1]).map(|k| (ranges[2 * k], ranges[2 * k + 1])).collect()))
+                      .collect())
+        }
+    }
+    /// `CausalGraph::intersect_with_summary(summary, frontier)` (src/causalgraph/summary.rs:234-264):
+    /// the common version as a frontier of local LVs, and what the summary's owner has that this
+    /// oplog lacks (None when nothing).
+    pub fn intersect_with_summary(&self, summary: &VersionSummary, frontier: &[u64])
+                                  -> Result<(Vec<u64>, Option<VersionSummary>), i32> {
+        let (mut names, mut name_off, mut range_off, mut ranges) = (Vec::<u8>::new(), vec![0usize], vec![0usize], Vec::<u64>::new());
+        for (name, rs) in summary {
+            names.extend_from_slice(name.as_bytes());
+            name_off.push(names.len());
+            for (a, b) in rs { ranges.push(*a); ranges.push(*b); }
+            range_off.push(ranges.len() / 2);
+        }
+        let entry_off = [0usize, summary.len()];
+        let version_off = [0usize, frontier.len()];
+        let s = dtgpu_summaries { doc: std::ptr::null(), entry_off: entry_off.as_ptr(), names: names.as_ptr(),
+                                  name_off: name_off.as_ptr(), range_off: range_off.as_ptr(), ranges: ranges.as_ptr(),
+                                  versions: frontier.as_ptr(), version_off: version_off.as_ptr() };
+        unsafe {
+            let (mut nf, mut nt) = (0usize, 0usize);
+            let st = dtgpu_oplog_intersect_summary(self.h, &s, 0, std::ptr::null_mut(), 0, &mut nf, std::ptr::null_mut(), 0, &mut nt);
+            if st != DTGPU_OK { return Err(st); }
+            let (mut f, mut t) = (vec![0u64; nf], vec![0u64; 3 * nt]);
+            let st = dtgpu_oplog_intersect_summary(self.h, &s, 0, f.as_mut_ptr(), nf, &mut nf, t.as_mut_ptr(), nt, &mut nt);
+            if st != DTGPU_OK { return Err(st); }
+            let mut rem: VersionSummary = Vec::new();
+            for r in t.chunks(3) {
+                let name = &summary[r[0] as usize].0;
+                match rem.last_mut() {
+                    Some(last) if &last.0 == name => last.1.push((r[1], r[2])),
+                    _ => rem.push((name.clone(), vec![(r[1], r[2])])),
+                }
+            }
+            Ok((f, if rem.is_empty() { None } else { Some(rem) }))
         }
     }
     fn export_u32(&self, what: c_int) -> Vec<u32> {

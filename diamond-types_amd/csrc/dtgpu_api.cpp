@@ -7,6 +7,7 @@
 #include <tuple>
 
 #include "dt_batch.hpp"
+#include "dt_summary.hpp"
 
 using namespace dtgpu;
 
@@ -683,6 +684,88 @@ int64_t dtgpu_oplog_remote_to_local(const dtgpu_oplog *h, uint32_t agent, uint64
         at = hi;
     }
     return at == end ? int64_t(k) : -1;
+}
+
+// AgentAssignment::summarize_versions (src/causalgraph/summary.rs:119-132)
+dtgpu_status dtgpu_oplog_summarize(const dtgpu_oplog *h, uint8_t *names, size_t names_cap, size_t *name_off,
+                                   size_t *range_off, size_t entry_cap, uint64_t *ranges, size_t range_cap,
+                                   size_t sizes[3]) {
+    if (!h) return DTGPU_ERR_ARG;
+    const HostOpLog &o = h->o;
+    const auto by = summarize_runs(o.agent_names.size(), o.agent_runs.size(), [&](size_t i, uint32_t &a, uint64_t &seq, uint64_t &len) {
+        a = o.agent_runs[i].agent; seq = o.agent_runs[i].seq; len = o.agent_runs[i].len;
+    });
+    const bool fit = write_summary(by, [&](size_t a, const uint8_t *&p, size_t &len) {
+        p = reinterpret_cast<const uint8_t *>(o.agent_names[a].data()); len = o.agent_names[a].size();
+    }, names, names_cap, name_off, range_off, entry_cap, ranges, range_cap, sizes);
+    return fit ? DTGPU_OK : DTGPU_ERR_ARG;
+}
+
+// CausalGraph::intersect_with_summary (src/causalgraph/summary.rs:234-264) over
+// intersect_with_summary_full (:175-208): the agent's runs in seq order, each one that overlaps a
+// range a known piece counting with the LV of its last seq, every uncovered stretch a remainder
+// record; then find_dominators over those LVs and the caller's.
+dtgpu_status dtgpu_oplog_intersect_summary(const dtgpu_oplog *h, const dtgpu_summaries *s, size_t i, uint64_t *frontier,
+                                           size_t frontier_cap, size_t *n_frontier, uint64_t *triples, size_t triple_cap,
+                                           size_t *n_triples) {
+    if (n_frontier) *n_frontier = 0;
+    if (n_triples) *n_triples = 0;
+    if (!h || !s || !s->entry_off || (!frontier && frontier_cap) || (!triples && triple_cap)) return DTGPU_ERR_ARG;
+    const HostOpLog &o = h->o;
+    const size_t e0 = s->entry_off[i], e1 = s->entry_off[i + 1];
+    if (e1 < e0 || (e1 > e0 && (!s->name_off || !s->range_off))) return DTGPU_ERR_ARG;
+    std::vector<uint64_t> lvs, rem;
+    for (size_t e = e0; e < e1; e++) {
+        if (s->name_off[e + 1] < s->name_off[e] || s->range_off[e + 1] < s->range_off[e]) return DTGPU_ERR_ARG;
+        if ((s->name_off[e + 1] > s->name_off[e] && !s->names) || (s->range_off[e + 1] > s->range_off[e] && !s->ranges))
+            return DTGPU_ERR_ARG;
+        const std::string name(reinterpret_cast<const char *>(s->names) + s->name_off[e], s->name_off[e + 1] - s->name_off[e]);
+        std::vector<AgentRun> runs;   // the named agent's runs, ascending seq
+        for (size_t a = 0; a < o.agent_names.size(); a++) {
+            if (o.agent_names[a] != name) continue;
+            for (const AgentRun &r : o.agent_runs) if (r.agent == a) runs.push_back(r);
+            break;
+        }
+        std::sort(runs.begin(), runs.end(), [](const AgentRun &a, const AgentRun &b) { return a.seq < b.seq; });
+        for (size_t k = s->range_off[e]; k < s->range_off[e + 1]; k++) {
+            const uint64_t rs = s->ranges[2 * k], re = s->ranges[2 * k + 1];
+            if (rs >= re) return DTGPU_ERR_ARG;
+            uint64_t next = rs;
+            for (const AgentRun &r : runs) {
+                if (r.seq >= re || r.seq + r.len <= rs) continue;
+                const uint64_t ps = std::max(rs, r.seq), pe = std::min(re, r.seq + r.len);
+                if (ps > next) rem.insert(rem.end(), {uint64_t(e - e0), next, ps});
+                next = pe;
+                lvs.push_back(r.lv + (pe - 1 - r.seq));
+            }
+            if (next < re) rem.insert(rem.end(), {uint64_t(e - e0), next, re});
+        }
+    }
+    if (s->version_off) {
+        if (s->version_off[i + 1] < s->version_off[i] || (s->version_off[i + 1] > s->version_off[i] && !s->versions))
+            return DTGPU_ERR_ARG;
+        lvs.insert(lvs.end(), s->versions + s->version_off[i], s->versions + s->version_off[i + 1]);
+    }
+    for (uint64_t v : lvs) if (v >= o.n_lv) return DTGPU_ERR_ARG;
+    {   // a graph entry is a chain: only its highest LV here can be a dominator
+        std::sort(lvs.begin(), lvs.end());
+        std::vector<uint64_t> top;
+        int64_t last = -1;
+        for (size_t j = lvs.size(); j-- > 0;) {
+            const int64_t e = o.graph.find_idx(lvs[j]);
+            if (e != last) top.push_back(lvs[j]);
+            last = e;
+        }
+        lvs.swap(top);
+    }
+    std::vector<uint64_t> dom(lvs.size() + 1);
+    const int64_t nd = dtgpu_oplog_dominators(h, lvs.data(), lvs.size(), nullptr, 0, dom.data(), dom.size());
+    if (nd < 0) return DTGPU_ERR_ARG;
+    for (size_t k = 0; k < size_t(nd) && k < frontier_cap; k++) frontier[k] = dom[k];
+    for (size_t k = 0; k < rem.size() && k < 3 * triple_cap; k++) triples[k] = rem[k];
+    if (n_frontier) *n_frontier = size_t(nd);
+    if (n_triples) *n_triples = rem.size() / 3;
+    return DTGPU_OK;
 }
 
 dtgpu_status dtgpu_oplog_history(const dtgpu_oplog *h, const uint64_t *version, size_t n_version, dtgpu_oplog **out) {

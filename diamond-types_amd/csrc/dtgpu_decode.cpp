@@ -20,6 +20,7 @@
 #include "dt_history.hpp"
 #include "dt_host.hpp"
 #include "dt_patch.hpp"
+#include "dt_request.hpp"
 
 using namespace dtgpu;
 
@@ -688,34 +689,51 @@ dtgpu_status dtgpu_decode_encode_from(const dtgpu_decoded *B, const uint32_t *do
         if (doc[i] >= B->n || version_off[i + 1] < version_off[i]) return DTGPU_ERR_ARG;
     const size_t n_req = n ? version_off[n] - version_off[0] : 0;
     if (n_req && !versions) return DTGPU_ERR_ARG;
-    auto M = new dtgpu_patches();
-    std::unique_ptr<dtgpu_patches> guard(M);
-    M->device = B->device;
-    M->n = n;
 #define CK(x) do { if (DTGPU_HIP_FAILED(x)) return DTGPU_ERR_HIP; } while (0)
-    CK(hipSetDevice(M->device));
+    CK(hipSetDevice(B->device));
     struct Own {
         hipStream_t s = nullptr;
-        hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-        ~Own() {
-            for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x);
-            if (s) (void)hipStreamDestroy(s);
-        }
+        ~Own() { if (s) (void)hipStreamDestroy(s); }
     } own;
     CK(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking));
-    for (hipEvent_t &e : own.e) CK(hipEventCreate(&e));
-    hipStream_t s = own.s;
-    std::vector<HistDesc> hd(n, HistDesc{});
+    MarkSetup setup;
+    mark_setup(*B, doc, n, setup);
     std::vector<uint32_t> req(n_req);
-    uint64_t scr = 0;
+    for (size_t i = 0; i < n; i++) {
+        HistDesc &h = setup.hd[i];
+        h.req_off = version_off[i] - version_off[0];
+        h.n_req = uint32_t(version_off[i + 1] - version_off[i]);
+        for (size_t k = version_off[i]; k < version_off[i + 1]; k++)
+            req[k - version_off[0]] = uint32_t(std::min<uint64_t>(versions[k], 0xFFFFFFFFull));
+    }
+    DevBuf<uint32_t> d_req;
+    DevBuf<HistDesc> d_hd;
+    CK(d_req.upload(req, own.s));
+    CK(d_hd.upload(setup.hd, own.s));
+#undef CK
+    return patches_from_requests(B, doc, n, flags, setup, d_hd.p, d_req.p, own.s, ms, out);
+}
+
+extern "C++" {
+namespace dtgpu {
+
+void hist_params_base(const dtgpu_decoded &B, HistParams &H) {
+    H.b_in = B.in.p; H.b_content = B.content.p; H.b_aruns = B.aruns.p; H.b_ops = B.ops.p; H.b_ent = B.ent.p;
+    H.b_poff = B.poff.p; H.b_par = B.par.p; H.b_cbyte = B.cbyte.p; H.b_agents = B.agents.p;
+}
+
+void mark_setup(const dtgpu_decoded &B, const uint32_t *doc, size_t n, MarkSetup &ms) {
+    ms.hd.assign(n, HistDesc{});
+    ms.scr_words = 0;
+    ms.lds_entries = 0;
     // the mark sweep's words: in LDS or in HBM scratch, by the history projection's rule and override
-    uint32_t lds_cap = HIST_LDS_ENTRIES, lds_entries = 0;
+    uint32_t lds_cap = HIST_LDS_ENTRIES;
     const uint32_t lds_form = getenv("DTGPU_MARK_AGENT_FENCE") ? 2u : 1u;   // (measurement: the sweep's earlier fence)
     if (const char *e = getenv("DTGPU_HISTORY_LDS_ENTRIES")) lds_cap = uint32_t(std::min<unsigned long>(strtoul(e, nullptr, 10), HIST_LDS_ENTRIES));
     for (size_t i = 0; i < n; i++) {
-        const DecodeDesc &bd = B->desc[doc[i]];
-        const DecodeResult &br = B->res[doc[i]];
-        HistDesc &h = hd[i];
+        const DecodeDesc &bd = B.desc[doc[i]];
+        const DecodeResult &br = B.res[doc[i]];
+        HistDesc &h = ms.hd[i];
         h.skip = br.status;
         h.b_in = bd.in_off; h.b_arun = bd.arun_off; h.b_op = bd.op_off; h.b_ent = bd.ent_off; h.b_poff = bd.poff_off;
         h.b_par = bd.par_off; h.b_content = bd.content_off; h.b_lv = bd.lv_off; h.b_agent = bd.agent_off;
@@ -724,36 +742,44 @@ dtgpu_status dtgpu_decode_encode_from(const dtgpu_decoded *B, const uint32_t *do
             h.b_n_par = br.n_parents; h.b_n_content = br.n_content; h.b_n_agents = br.n_agents;
             h.b_n_lv = uint32_t(std::min<uint64_t>(br.n_lv, 0xFFFFFFFFull)); h.b_complete = br.content_complete;
         }
-        h.req_off = version_off[i] - version_off[0];
-        h.n_req = uint32_t(version_off[i + 1] - version_off[i]);
-        for (size_t k = version_off[i]; k < version_off[i + 1]; k++)
-            req[k - version_off[0]] = uint32_t(std::min<uint64_t>(versions[k], 0xFFFFFFFFull));
         h.use_lds = h.b_n_ent <= lds_cap ? lds_form : 0u;
-        if (h.use_lds && !h.skip) lds_entries = std::max(lds_entries, h.b_n_ent);
-        h.scr_off = scr;
-        scr += uint64_t(HIST_ENT_WORDS) * h.b_n_ent;
+        if (h.use_lds && !h.skip) ms.lds_entries = std::max(ms.lds_entries, h.b_n_ent);
+        h.scr_off = ms.scr_words;
+        ms.scr_words += uint64_t(HIST_ENT_WORDS) * h.b_n_ent;
         h.o_ver = uint64_t(DECODE_MAX_FRONTIER) * i;
     }
-    DevBuf<uint32_t> d_req, d_scr, d_ver, d_w;
+}
+
+dtgpu_status patches_from_requests(const dtgpu_decoded *B, const uint32_t *doc, size_t n, uint32_t flags,
+                                   const MarkSetup &setup, const HistDesc *d_hd, const uint32_t *d_req, hipStream_t s,
+                                   float *ms, dtgpu_patches **out, MarkOut *mark) {
+    const std::vector<HistDesc> &hd = setup.hd;
+    auto M = new dtgpu_patches();
+    std::unique_ptr<dtgpu_patches> guard(M);
+    M->device = B->device;
+    M->n = n;
+#define CK(x) do { if (DTGPU_HIP_FAILED(x)) return DTGPU_ERR_HIP; } while (0)
+    struct Own {
+        hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+        ~Own() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+    } own;
+    for (hipEvent_t &e : own.e) CK(hipEventCreate(&e));
+    DevBuf<uint32_t> d_scr, d_ver, d_w;
     DevBuf<uint8_t> d_b;
-    DevBuf<HistDesc> d_hd;
     DevBuf<PatchDesc> d_pd;
     DevBuf<PatchCounts> d_cnt;
     DevBuf<PatchResult> d_res;
-    CK(d_req.upload(req, s));
-    CK(d_scr.alloc(scr));
-    CK(d_hd.upload(hd, s));
+    CK(d_scr.alloc(setup.scr_words));
     CK(d_ver.alloc(uint64_t(DECODE_MAX_FRONTIER) * n));
     CK(M->front.alloc(uint64_t(DECODE_MAX_FRONTIER) * n));
     CK(d_cnt.alloc(n));
     CK(d_res.alloc(n));
     PatchParams P{};
     HistParams &H = P.H;
-    H.b_in = B->in.p; H.b_content = B->content.p; H.b_aruns = B->aruns.p; H.b_ops = B->ops.p; H.b_ent = B->ent.p;
-    H.b_poff = B->poff.p; H.b_par = B->par.p; H.b_cbyte = B->cbyte.p; H.b_agents = B->agents.p;
-    H.req = d_req.p; H.scr = d_scr.p; H.o_ver = d_ver.p; H.o_front = M->front.p;
-    H.docs = d_hd.p; H.n_docs = uint32_t(n);
-    P.counts = d_cnt.p; P.results = d_res.p; P.n_docs = uint32_t(n); P.lds_entries = lds_entries;
+    hist_params_base(*B, H);
+    H.req = d_req; H.scr = d_scr.p; H.o_ver = d_ver.p; H.o_front = M->front.p;
+    H.docs = d_hd; H.n_docs = uint32_t(n);
+    P.counts = d_cnt.p; P.results = d_res.p; P.n_docs = uint32_t(n); P.lds_entries = setup.lds_entries;
     P.prof = getenv("DTGPU_PATCH_PROF") ? 1u : 0u;   // read at call time: the build waves count their phase cycles
     P.flags = flags & (DTGPU_ENCODE_STORE_INSERTED_CONTENT | DTGPU_ENCODE_COMPRESS_CONTENT);
     crc_x2n(P.x2n);
@@ -804,6 +830,10 @@ dtgpu_status dtgpu_decode_encode_from(const dtgpu_decoded *B, const uint32_t *do
     CK(hipEventRecord(own.e[3], s));
     M->res.assign(n, PatchResult{});
     if (n) CK(hipMemcpyAsync(M->res.data(), d_res.p, n * sizeof(PatchResult), hipMemcpyDeviceToHost, s));
+    if (mark) {
+        mark->front.assign(size_t(DECODE_MAX_FRONTIER) * n, 0);
+        if (n) CK(hipMemcpyAsync(mark->front.data(), M->front.p, mark->front.size() * 4, hipMemcpyDeviceToHost, s));
+    }
     CK(hipStreamSynchronize(s));
     float t0 = 0, t1 = 0;
     CK(hipEventElapsedTime(&t0, own.e[0], own.e[1]));
@@ -813,12 +843,20 @@ dtgpu_status dtgpu_decode_encode_from(const dtgpu_decoded *B, const uint32_t *do
     for (size_t i = 0; i < n; i++) M->n_front[i] = cnt[i].status ? 0u : cnt[i].n_front;
     M->form.assign(n, 0);
     for (size_t i = 0; i < n; i++) M->form[i] = cnt[i].form;
+    if (mark) {
+        mark->status.assign(n, 0);
+        for (size_t i = 0; i < n; i++) mark->status[i] = cnt[i].status;
+        mark->n_front = M->n_front;
+    }
     M->mark_ms = t0;
     M->build_ms = t1;
     if (ms) *ms = t0 + t1;
     *out = guard.release();
     return DTGPU_OK;
 }
+
+}  // namespace dtgpu
+}  // extern "C++"
 
 size_t dtgpu_patches_size(const dtgpu_patches *p) { return p ? p->n : 0; }
 

@@ -69,6 +69,14 @@ class GraphAnswer(ctypes.Structure):
 _lib = None
 
 
+class Summaries(ctypes.Structure):
+    """dtgpu_summaries (include/dtgpu.h): a batch of version summaries, flattened."""
+    _fields_ = [("doc", ctypes.POINTER(ctypes.c_uint32)), ("entry_off", ctypes.POINTER(ctypes.c_size_t)),
+                ("names", ctypes.c_char_p), ("name_off", ctypes.POINTER(ctypes.c_size_t)),
+                ("range_off", ctypes.POINTER(ctypes.c_size_t)), ("ranges", ctypes.POINTER(ctypes.c_uint64)),
+                ("versions", ctypes.POINTER(ctypes.c_uint64)), ("version_off", ctypes.POINTER(ctypes.c_size_t))]
+
+
 def _check_build_record():
     """The library's build record (lib/build_info.json, tools/build_info.py) names the hash of every
     source it was built from: a library built from other sources than the ones beside it (a stale
@@ -235,6 +243,19 @@ def lib():
     L.dtgpu_patches_profile.argtypes = [vp, sz, ctypes.POINTER(ctypes.c_uint32)]
     L.dtgpu_patches_free.argtypes = [vp]
     L.dtgpu_batch_create_decoded.argtypes = [vp, ctypes.POINTER(vp)]
+    psz, pf, psum = ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(Summaries)
+    L.dtgpu_oplog_summarize.argtypes = [vp, ctypes.c_char_p, sz, psz, psz, sz, pu64, sz, psz]
+    L.dtgpu_oplog_intersect_summary.argtypes = [vp, psum, sz, pu64, sz, psz, pu64, sz, psz]
+    L.dtgpu_decode_summarize.argtypes = [vp, sz, ctypes.c_char_p, sz, psz, psz, sz, pu64, sz, psz]
+    L.dtgpu_decode_intersect.argtypes = [vp, psum, sz, pf, ctypes.POINTER(vp)]
+    L.dtgpu_decode_encode_from_summaries.argtypes = [vp, psum, sz, ctypes.c_uint32, pf, ctypes.POINTER(vp),
+                                                     ctypes.POINTER(vp)]
+    L.dtgpu_intersect_size.argtypes = [vp]
+    L.dtgpu_intersect_size.restype = sz
+    L.dtgpu_intersect_result.argtypes = [vp, sz, pu64, sz, psz]
+    L.dtgpu_intersect_remainder.argtypes = [vp, sz, pu64, sz, psz]
+    L.dtgpu_intersect_profile.argtypes = [vp, sz, pu32]
+    L.dtgpu_intersect_free.argtypes = [vp]
     L.dtgpu_graph_queries.argtypes = [ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(sz), sz,
                                       ctypes.POINTER(GraphQuery), sz, ctypes.POINTER(ctypes.c_int64), sz,
                                       ctypes.POINTER(ctypes.c_int64), sz,
@@ -252,6 +273,88 @@ def _check(code):
 
 def _u64s(xs):
     return (ctypes.c_uint64 * max(1, len(xs)))(*xs), len(xs)
+
+
+def _name_bytes(name) -> bytes:
+    return bytes(name) if isinstance(name, (bytes, bytearray)) else str(name).encode()
+
+
+def normalize_summary(summary):
+    """A version summary as [(name bytes, [(start, end), ...])].  Accepts VersionSummary entries
+    (name, ranges) and VersionSummaryFlat entries (name, next_seq), which stand for
+    name: [(0, next_seq)] (src/causalgraph/summary.rs:13-30)."""
+    out = []
+    for name, x in summary:
+        if isinstance(x, int):
+            rs = [(0, x)] if x else []
+        else:
+            rs = [(int(a), int(b)) for a, b in x]
+        out.append((_name_bytes(name), rs))
+    return out
+
+
+def summary_of_remote_frontier(rf):
+    """A remote frontier [(name, seq)] as the summary of unit ranges name: [(seq, seq + 1)]."""
+    return [(_name_bytes(name), [(int(q), int(q) + 1)]) for name, q in rf]
+
+
+def _pack_summaries(summaries, docs=None, frontiers=None):
+    """The flattened dtgpu_summaries of a list of normalized summaries; returns (struct, names per
+    request).  The struct keeps its arrays alive."""
+    n = len(summaries)
+    entry_off, name_off, range_off, ranges, blob, names = [0], [0], [0], [], bytearray(), []
+    for sm in summaries:
+        names.append([nm for nm, _ in sm])
+        for nm, rs in sm:
+            blob += nm
+            name_off.append(len(blob))
+            for a, b in rs:
+                ranges += [a, b]
+            range_off.append(len(ranges) // 2)
+        entry_off.append(len(name_off) - 1)
+    S = Summaries()
+    S._keep = [(ctypes.c_uint32 * max(n, 1))(*[int(d) for d in (docs if docs is not None else [0] * n)]),
+               (ctypes.c_size_t * (n + 1))(*entry_off), bytes(blob),
+               (ctypes.c_size_t * len(name_off))(*name_off), (ctypes.c_size_t * len(range_off))(*range_off),
+               (ctypes.c_uint64 * max(1, len(ranges)))(*ranges)]
+    S.doc, S.entry_off, S.names, S.name_off, S.range_off, S.ranges = S._keep
+    if frontiers is not None:
+        if len(frontiers) != n:
+            raise ValueError("one frontier per summary")
+        flat, off = [], [0]
+        for f in frontiers:
+            flat.extend(int(x) for x in f)
+            off.append(len(flat))
+        S._keep += [(ctypes.c_uint64 * max(1, len(flat)))(*flat), (ctypes.c_size_t * (n + 1))(*off)]
+        S.versions, S.version_off = S._keep[-2:]
+    return S, names
+
+
+def _group_remainder(names, triples):
+    """Remainder records (entry, start, end) -> [(name, [(start, end), ...])] as
+    intersect_with_summary groups them (summary.rs:246-255): consecutive records of equal name
+    merge into one entry.  No records: None."""
+    out = []
+    for e, a, b in triples:
+        nm = names[e].decode(errors="surrogateescape")
+        if out and out[-1][0] == nm:
+            out[-1][1].append((a, b))
+        else:
+            out.append((nm, [(a, b)]))
+    return out or None
+
+
+def _read_summary(call):
+    """dtgpu_oplog_summarize's query-size protocol -> [(name, [(start, end), ...])]."""
+    sizes = (ctypes.c_size_t * 3)()
+    _check(call(None, 0, None, None, 0, None, 0, sizes))
+    ne, nb, nr = sizes[0], sizes[1], sizes[2]
+    names = ctypes.create_string_buffer(max(1, nb))
+    name_off, range_off = (ctypes.c_size_t * (ne + 1))(), (ctypes.c_size_t * (ne + 1))()
+    ranges = (ctypes.c_uint64 * max(1, 2 * nr))()
+    _check(call(names, nb, name_off, range_off, ne, ranges, nr, sizes))
+    return [(names.raw[name_off[e]:name_off[e + 1]].decode(errors="surrogateescape"),
+             [(ranges[2 * k], ranges[2 * k + 1]) for k in range(range_off[e], range_off[e + 1])]) for e in range(ne)]
 
 
 def text_hash(data: bytes) -> int:
@@ -652,6 +755,41 @@ class ListOpLog:
                 return [(buf[2 * i], buf[2 * i + 1]) for i in range(k)]
             cap = k
 
+    def summarize_versions(self):
+        """AgentAssignment::summarize_versions (src/causalgraph/summary.rs:119-132):
+        [(name, [(seq start, seq end), ...])] per agent with ops, in agent-id order."""
+        return _read_summary(lambda *a: lib().dtgpu_oplog_summarize(self._h, *a))
+
+    def intersect_with_summary(self, summary, frontier=()):
+        """CausalGraph::intersect_with_summary (src/causalgraph/summary.rs:234-264): (the version the
+        summary's owner and this oplog share, as a frontier of local LVs; what the owner has and
+        this oplog lacks as [(name, ranges)], or None).  `summary` may be flat, [(name, next_seq)]."""
+        st, f, triples = self.intersect_summary_records(summary, frontier)
+        _check(st)
+        return f, _group_remainder([nm for nm, _ in normalize_summary(summary)], triples)
+
+    def intersect_summary_records(self, summary, frontier=()):
+        """dtgpu_oplog_intersect_summary as it is: (status, frontier, remainder records (entry index,
+        start, end)) -- what the batched device call is compared with, request for request."""
+        S, _ = _pack_summaries([normalize_summary(summary)], frontiers=[list(frontier)])
+        nf, nt = ctypes.c_size_t(), ctypes.c_size_t()
+        st = lib().dtgpu_oplog_intersect_summary(self._h, ctypes.byref(S), 0, None, 0, ctypes.byref(nf), None, 0,
+                                                 ctypes.byref(nt))
+        if st:
+            return st, [], []
+        f, t = (ctypes.c_uint64 * max(1, nf.value))(), (ctypes.c_uint64 * max(1, 3 * nt.value))()
+        st = lib().dtgpu_oplog_intersect_summary(self._h, ctypes.byref(S), 0, f, nf.value, ctypes.byref(nf), t,
+                                                 nt.value, ctypes.byref(nt))
+        return st, list(f[:nf.value]), [(t[3 * k], t[3 * k + 1], t[3 * k + 2]) for k in range(nt.value)]
+
+    def remote_frontier_to_local(self, rf, frontier=()):
+        """A remote frontier [(name, seq)] as a frontier of local LVs; KeyError when this oplog
+        lacks one of those versions."""
+        f, rem = self.intersect_with_summary(summary_of_remote_frontier(rf), frontier)
+        if rem is not None:
+            raise KeyError(rem)
+        return f
+
     def checkout_text_bytes(self, spans) -> bytes:
         """OpLog::checkout_text (src/oplog.rs:388-394) for the text whose ops are `spans`: the
         projected sub-oplog checked out on the device."""
@@ -997,6 +1135,36 @@ class DecodeBatch:
         _check(lib().dtgpu_decode_encode_from(self._h, d, pv, po, n, flags, ctypes.byref(ms), ctypes.byref(h)))
         return PatchBatch(h, n, ms.value)
 
+    def summarize_versions(self, i):
+        """AgentAssignment::summarize_versions of resident document i (dtgpu_decode_summarize)."""
+        return _read_summary(lambda *a: lib().dtgpu_decode_summarize(self._h, i, *a))
+
+    def intersect(self, docs, summaries, frontiers=None, remote_frontier=False):
+        """CausalGraph::intersect_with_summary for a whole batch, on the GPU (dtgpu_decode_intersect):
+        summaries[i] (as ListOpLog.intersect_with_summary takes it; with remote_frontier a remote
+        frontier [(name, seq)]) met with document docs[i]; frontiers[i] are extra LVs of that
+        document.  Returns an IntersectBatch."""
+        if len(summaries) != len(docs):
+            raise ValueError("one summary per document index")
+        sms = [summary_of_remote_frontier(x) if remote_frontier else normalize_summary(x) for x in summaries]
+        S, names = _pack_summaries(sms, docs, frontiers)
+        ms, h = ctypes.c_float(), ctypes.c_void_p()
+        _check(lib().dtgpu_decode_intersect(self._h, ctypes.byref(S), len(docs), ctypes.byref(ms), ctypes.byref(h)))
+        return IntersectBatch(h, len(docs), ms.value, names)
+
+    def sync(self, docs, summaries, opts=None, frontiers=None):
+        """The whole answer to a batch of sync hellos (dtgpu_decode_encode_from_summaries):
+        (PatchBatch of what each peer lacks, IntersectBatch of the common frontiers and of what
+        each peer has that this side lacks).  opts defaults to ENCODE_PATCH."""
+        if len(summaries) != len(docs):
+            raise ValueError("one summary per document index")
+        S, names = _pack_summaries([normalize_summary(x) for x in summaries], docs, frontiers)
+        ms, hp, hx = ctypes.c_float(), ctypes.c_void_p(), ctypes.c_void_p()
+        flags = (opts or ENCODE_PATCH).flags()
+        _check(lib().dtgpu_decode_encode_from_summaries(self._h, ctypes.byref(S), len(docs), flags, ctypes.byref(ms),
+                                                        ctypes.byref(hp), ctypes.byref(hx)))
+        return PatchBatch(hp, len(docs), ms.value), IntersectBatch(hx, len(docs), ms.value, names)
+
     def checkout_versions(self, docs, versions):
         """ListOpLog::checkout(versions[i]) of document docs[i] for a whole batch: the histories
         projected on the GPU (history), then one device-staged checkout batch.  Returns the
@@ -1085,6 +1253,63 @@ class PatchBatch:
         buf = ctypes.create_string_buffer(max(1, n.value))
         _check(lib().dtgpu_patches_get(self._h, i, buf, n.value, ctypes.byref(n)))
         return buf.raw[:n.value]
+
+
+class IntersectBatch:
+    """The intersections of one DecodeBatch.intersect / sync call (dtgpu_intersect)."""
+
+    def __init__(self, handle, n, last_ms, names):
+        self._h, self.n, self.last_ms, self._names = handle, n, last_ms, names
+
+    def __len__(self):
+        return self.n
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            lib().dtgpu_intersect_free(h)
+            self._h = None
+
+    def _result(self, i):
+        k = ctypes.c_size_t()
+        buf = (ctypes.c_uint64 * 64)()
+        st = lib().dtgpu_intersect_result(self._h, i, buf, 64, ctypes.byref(k))
+        return st, list(buf[:k.value])
+
+    def status(self, i) -> int:
+        return self._result(i)[0]
+
+    def frontier(self, i):
+        """The version request i's peer and the document share, in the document's LVs, ascending."""
+        return self._result(i)[1]
+
+    def remainder_records(self, i):
+        """Request i's remainder as (entry index, start, end) records, in visiting order."""
+        k = ctypes.c_size_t()
+        lib().dtgpu_intersect_remainder(self._h, i, None, 0, ctypes.byref(k))
+        buf = (ctypes.c_uint64 * max(1, 3 * k.value))()
+        lib().dtgpu_intersect_remainder(self._h, i, buf, k.value, ctypes.byref(k))
+        return [(buf[3 * j], buf[3 * j + 1], buf[3 * j + 2]) for j in range(k.value)]
+
+    def remainder(self, i):
+        """What request i's peer has and the document lacks: [(name, ranges)], or None."""
+        return _group_remainder(self._names[i], self.remainder_records(i))
+
+    def local_frontier(self, i):
+        """frontier(i) of a remote-frontier request; KeyError when the document lacks part of it."""
+        st, f = self._result(i)
+        _check(st)
+        rem = self.remainder(i)
+        if rem is not None:
+            raise KeyError(rem)
+        return f
+
+    def profile(self, i):
+        """dtgpu_intersect_profile: [known pieces, remainder records, re-ordered ranges, count us,
+        emit us, mark us, 0, 0]."""
+        out = (ctypes.c_uint32 * 8)()
+        _check(lib().dtgpu_intersect_profile(self._h, i, out))
+        return list(out)
 
 
 GQ_KINDS = {"diff": 0, "conflict": 1, "contains": 2, "dominators": 3, "diff_level": 4, "conflict_level": 5}

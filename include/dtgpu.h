@@ -213,6 +213,44 @@ dtgpu_status dtgpu_oplog_local_to_remote(const dtgpu_oplog *oplog, uint64_t lv, 
  * their count, or -1 when part of the span is unknown to this oplog. */
 int64_t dtgpu_oplog_remote_to_local(const dtgpu_oplog *oplog, uint32_t agent, uint64_t seq, uint64_t n,
                                     uint64_t *spans, size_t cap);
+/* A batch of version summaries (VersionSummary, src/causalgraph/summary.rs:13-30), flattened: what a
+ * peer that knows no local LVs says it holds.  Request i is the entries entry_off[i] ..
+ * entry_off[i+1]; entry k is the agent name names[name_off[k] .. name_off[k+1]) with the seq ranges
+ * {start, end} ranges[2r], ranges[2r+1] for r in range_off[k] .. range_off[k+1], in the order
+ * given; versions[version_off[i] .. version_off[i+1]) are extra LVs of the request's document (the
+ * `frontier: &[LV]` argument of intersect_with_summary).  All offset arrays ascend.  doc is read by
+ * the batched calls only (dtgpu_decode_intersect, dtgpu_decode_encode_from_summaries). */
+typedef struct dtgpu_summaries {
+    const uint32_t *doc;              /* n: resident document of request i (may repeat, any order) */
+    const size_t   *entry_off;        /* n + 1: entries of request i */
+    const uint8_t  *names;            /* all entries' name bytes, back to back */
+    const size_t   *name_off;         /* entries + 1 */
+    const size_t   *range_off;        /* entries + 1 */
+    const uint64_t *ranges;           /* pairs {start, end} */
+    const uint64_t *versions;         /* extra LVs, or NULL */
+    const size_t   *version_off;      /* n + 1, or NULL */
+} dtgpu_summaries;
+/* AgentAssignment::summarize_versions (src/causalgraph/summary.rs:119-132): per agent with ops, in
+ * agent-id order, its name and its seq ranges, sorted and merged where adjacent (merge_spans,
+ * :124-128), in the dtgpu_summaries layout of one request (name_off and range_off hold entries + 1
+ * offsets from 0).  sizes[0..2] = entries, name bytes, ranges, always written; buffers may be NULL
+ * to query them; DTGPU_ERR_ARG when a non-NULL buffer's cap (names: bytes; name_off / range_off:
+ * entry_cap + 1 offsets each; ranges: range_cap pairs) is too small. */
+dtgpu_status dtgpu_oplog_summarize(const dtgpu_oplog *oplog, uint8_t *names, size_t names_cap, size_t *name_off,
+                                   size_t *range_off, size_t entry_cap, uint64_t *ranges, size_t range_cap,
+                                   size_t sizes[3]);
+/* CausalGraph::intersect_with_summary(summary, frontier) (src/causalgraph/summary.rs:234-264, over
+ * intersect_with_summary_full, :175-208) for request i of s: every range is cut into the pieces this
+ * oplog knows (one per agent run it overlaps, each counting with the LV of its last seq, :242) and
+ * the stretches it does not (unknown names whole).  frontier = find_dominators(those LVs and the
+ * extra LVs), ascending: what the peer and this oplog both have.  triples = the remainder, what the
+ * peer has and this oplog lacks: records {entry index within the request, start, end} in visiting
+ * order, never merged across ranges (*n_triples = 0: the reference's None).  Writes min(count, cap)
+ * and the counts.  DTGPU_ERR_ARG for a range with start >= end and for an extra LV outside the
+ * oplog.  Plain host code; the batched device calls are compared with it. */
+dtgpu_status dtgpu_oplog_intersect_summary(const dtgpu_oplog *oplog, const dtgpu_summaries *s, size_t i,
+                                           uint64_t *frontier, size_t frontier_cap, size_t *n_frontier,
+                                           uint64_t *triples, size_t triple_cap, size_t *n_triples);
 /* The history of `version` as an oplog of its own (what ListOpLog::checkout(&[LV]) replays:
  * diff_rev(version, ROOT), src/causalgraph/graph/tools.rs:176-292), LVs compacted in order,
  * agents / seqs / positions unchanged; its tip checkout is the checkout at `version`. */
@@ -504,6 +542,53 @@ dtgpu_status dtgpu_patches_get(const dtgpu_patches *p, size_t i, uint8_t *out, s
  * write + CRC.  out[11] = 0. */
 dtgpu_status dtgpu_patches_profile(const dtgpu_patches *p, size_t i, uint32_t out[12]);
 void dtgpu_patches_free(dtgpu_patches *p);
+/* CausalGraph::intersect_with_summary (src/causalgraph/summary.rs:175-264) for a batch, on the GPU:
+ * request i is a peer's summary s (request i of the flattened layout) met with resident document
+ * s->doc[i] of `base` (any handle dtgpu_decode_encode_from accepts; unchanged).  One wavefront per
+ * request (dt_summary.hip) resolves the names against the document's agents, clips every range
+ * against the agent's runs and writes the known pieces' LVs and the extra LVs as the request's LV
+ * set in HBM, the remainder records beside it; the history mark launch (dt_history.hip) then
+ * reduces each LV set to its dominators (find_dominators, :261).  The LV sets never visit the host.
+ * For every request the status, the frontier and the remainder equal dtgpu_oplog_intersect_summary
+ * on a host oplog of that document.  Per-request status: the base document's own when that is not 0;
+ * DTGPU_ERR_ARG for a range with start >= end and for an extra LV >= the document's LV count;
+ * DTGPU_DECODE_DEFER when the reduced frontier is wider than 64; DTGPU_ERR_CAPACITY when a
+ * reservation proves too small.  A failed request never fails the batch; the request with no
+ * entries and no extra LVs is ROOT (empty frontier, no remainder).  *ms = the device time of the
+ * call's kernels (the two summary launches and the mark). */
+typedef struct dtgpu_intersect dtgpu_intersect;
+dtgpu_status dtgpu_decode_intersect(const dtgpu_decoded *base, const dtgpu_summaries *s, size_t n, float *ms,
+                                    dtgpu_intersect **out);
+size_t dtgpu_intersect_size(const dtgpu_intersect *x);
+/* Request i's status and its common frontier (summary.rs:261), in the base document's LVs,
+ * ascending: writes min(len, cap) LVs and the length. */
+dtgpu_status dtgpu_intersect_result(const dtgpu_intersect *x, size_t i, uint64_t *frontier, size_t cap,
+                                    size_t *n_frontier);
+/* Request i's remainder (summary.rs:245-256) as records {entry index within the request, start,
+ * end}: writes min(count, cap) records and the count (0: None); returns the request's status. */
+dtgpu_status dtgpu_intersect_remainder(const dtgpu_intersect *x, size_t i, uint64_t *triples, size_t cap, size_t *n);
+/* Where request i's work went: out[0] = known pieces, out[1] = remainder records, out[2] = ranges
+ * whose pieces were not in seq order (ranked by counting), out[3], out[4] = the summary count and
+ * emit launches' us (whole batch), out[5] = the mark launch's us (dtgpu_decode_intersect; the
+ * fused call's mark is in dtgpu_patches_profile), out[6], out[7] = 0. */
+dtgpu_status dtgpu_intersect_profile(const dtgpu_intersect *x, size_t i, uint32_t out[8]);
+void dtgpu_intersect_free(dtgpu_intersect *x);
+/* The whole answer to a batch of sync hellos (summary.rs:234-264, then ListOpLog::encode_from,
+ * src/list/encoding/encode_oplog.rs:404-747): the summary launches of dtgpu_decode_intersect feed
+ * the patch path of dtgpu_decode_encode_from in HBM, so *patches holds, per request, the `.dt` patch
+ * of everything the peer lacks (byte-equal to dtgpu_decode_encode_from at the common frontier;
+ * flags and statuses as there) and *isect the common frontiers and remainders.  *ms = the device
+ * time of all four kernels. */
+dtgpu_status dtgpu_decode_encode_from_summaries(const dtgpu_decoded *base, const dtgpu_summaries *s, size_t n,
+                                                uint32_t flags, float *ms, dtgpu_patches **patches,
+                                                dtgpu_intersect **isect);
+/* AgentAssignment::summarize_versions (src/causalgraph/summary.rs:119-132) of resident document i,
+ * with dtgpu_oplog_summarize's buffers and protocol; returns the document's status when that is not
+ * 0.  Host code over one copy of the document's agent runs and names: the output is a few ranges
+ * and needs a sort per agent, so this is not a kernel and not a hot path. */
+dtgpu_status dtgpu_decode_summarize(const dtgpu_decoded *base, size_t i, uint8_t *names, size_t names_cap,
+                                    size_t *name_off, size_t *range_off, size_t entry_cap, uint64_t *ranges,
+                                    size_t range_cap, size_t sizes[3]);
 /* A device-staged checkout batch over a decoded handle (consumed, also on failure): decoded here
  * unless it already holds merged oplogs; then as dtgpu_batch_create_device. */
 dtgpu_status dtgpu_batch_create_decoded(dtgpu_decoded *dec, dtgpu_batch **out);
