@@ -25,6 +25,10 @@ pub struct dtgpu_patches {
 pub struct dtgpu_intersect {
     _p: [u8; 0],
 }
+#[repr(C)]
+pub struct dtgpu_merges {
+    _p: [u8; 0],
+}
 /// A batch of version summaries, flattened (include/dtgpu.h `dtgpu_summaries`).
 #[repr(C)]
 pub struct dtgpu_summaries {
@@ -178,6 +182,17 @@ extern "C" {
     pub fn dtgpu_decode_summarize(base: *const dtgpu_decoded, i: usize, names: *mut u8, names_cap: usize,
                                   name_off: *mut usize, range_off: *mut usize, entry_cap: usize, ranges: *mut u64,
                                   range_cap: usize, sizes: *mut usize) -> dtgpu_status;
+    // batched iter_xf_operations_from / ListBranch::merge over resident documents
+    pub fn dtgpu_decode_xf_from(base: *const dtgpu_decoded, docs: *const u32, from: *const u64, from_off: *const usize,
+                                merging: *const u64, merging_off: *const usize, n: usize, kernel_ms: *mut f32,
+                                out: *mut *mut dtgpu_merges) -> dtgpu_status;
+    pub fn dtgpu_merges_size(m: *const dtgpu_merges) -> usize;
+    pub fn dtgpu_merges_result(m: *const dtgpu_merges, i: usize, frontier: *mut u64, cap: usize,
+                               n_frontier: *mut usize) -> dtgpu_status;
+    pub fn dtgpu_merges_ops(m: *const dtgpu_merges, i: usize, out: *mut u32, cap: usize, n_out: *mut usize) -> dtgpu_status;
+    pub fn dtgpu_merges_text(m: *const dtgpu_merges, i: usize, out: *mut u8, cap: usize, out_len: *mut usize) -> dtgpu_status;
+    pub fn dtgpu_merges_profile(m: *const dtgpu_merges, i: usize, out: *mut u32) -> dtgpu_status;
+    pub fn dtgpu_merges_free(m: *mut dtgpu_merges);
     pub fn dtgpu_device_count() -> c_int;
     // the decoded oplog's arrays (op runs, inserted content, per-LV byte offsets, ...)
     pub fn dtgpu_oplog_export(oplog: *const dtgpu_oplog, what: c_int, out: *mut c_void, cap: usize) -> usize;

@@ -239,7 +239,9 @@ namespace dtgpu {
 // Host-staged batch: decoded oplogs -> uploaded planner arrays -> planner sizing pass -> replay
 // layout.  xf: a transformed-ops batch (iter_xf_operations).
 dtgpu_status stage(std::vector<Prepared> &prep, const dtgpu_batch_opts *opts, dtgpu_batch **out, bool xf = false);
-// Device-staged batch over a decoded handle, which the batch consumes.
-dtgpu_status stage_device(dtgpu_decoded *dec, const dtgpu_batch_opts *opts, dtgpu_batch **out);
+// Device-staged batch over a decoded handle, which the batch consumes.  xf: the merge form
+// (dt_merge.hpp), the handle's documents being the requests' projected histories.
+struct XfStage;
+dtgpu_status stage_device(dtgpu_decoded *dec, const dtgpu_batch_opts *opts, dtgpu_batch **out, XfStage *xf = nullptr);
 
 }  // namespace dtgpu

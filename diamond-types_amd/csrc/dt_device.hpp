@@ -172,11 +172,14 @@ struct PlanDesc {       // per document; offsets index the concatenated PlanInpu
     uint32_t ne, n_agents, n_aruns, ntip, n_lv, ccap, tcap, skip;
     uint32_t row_stride, pad;
     uint64_t coff_off, poff_off;   // device staging: per entry children (prep scratch), parent offsets (decoder)
+    uint64_t xf_off;               // plan_kernel_xf: the request's `from` in PlanParams::xf_from (n_from LVs)
+    uint32_t n_from, pad2;
 };
 struct PlanResult {
     uint32_t status, ncmd, ntlist, n_tip;
     uint64_t n_retreat, n_advance;
     uint64_t prof[6];   // DTGPU_PLAN_PROF: cycles in record wait, parents, children+pick, emit, ops, init
+    uint32_t xf_first, n_xf;   // plan_kernel_xf: the first reported command, the reported LVs
 };
 struct PlanParams {
     const uint32_t *par, *pent, *pch, *pcnt, *child, *aruns, *tip, *erec, *doff, *dense;
@@ -199,6 +202,10 @@ struct PlanParams {
     PlanResult *results;
     uint32_t n_docs, count_only;   // n_docs: the grid (the list's length when doc_list is set)
     const uint32_t *doc_list;      // nullable: block i plans docs[doc_list[i]]
+    // merge requests (dtgpu_decode_xf_from): every document is the projected history of a request
+    // and plan_kernel_xf plans it; xf_from holds the requests' `from` versions in projected LVs
+    uint32_t xf;
+    const uint32_t *xf_from;
 };
 int launch_plan(const PlanParams &q, void *stream, bool walk = true);
 // walk_kernel alone; csr: children and parent counts from prep's CSR (ready after prep's first

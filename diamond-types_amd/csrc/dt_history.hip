@@ -61,9 +61,10 @@ struct Out {
 };
 
 // Graph entries: an included entry starts a new entry unless its only (mapped) parent is the
-// previous new LV (Graph::push); parents mapped in order (the map is monotone).
+// previous new LV (Graph::push); parents mapped in order (the map is monotone).  keep: every
+// included entry stays an entry of its own (HistParams::keep_entries).
 __device__ __forceinline__ bool emit_entries(const HistDesc &D, const Base &B, const Scr &S, const Out &O, uint32_t n_lv,
-                                             uint32_t &n_ent, uint32_t &n_par) {
+                                             uint32_t &n_ent, uint32_t &n_par, bool keep) {
     const uint32_t L = lane();
     uint32_t nh = 0, np_tot = 0;
     bool over = false;
@@ -75,7 +76,7 @@ __device__ __forceinline__ bool emit_entries(const HistDesc &D, const Base &B, c
         const uint32_t nbv = inc ? S.nb[e] : 0;
         const uint32_t p0 = inc ? B.poff[e] : 0, np = inc ? B.poff[e + 1] - p0 : 0;
         const uint32_t m0 = np ? map_lv(B, S, B.par[p0]) : NONE;
-        const bool head = inc && !(np == 1 && m0 + 1 == nbv);
+        const bool head = inc && (keep || !(np == 1 && m0 + 1 == nbv));
         if (valid) S.head[e] = head ? 1u : 0u;
         const uint64_t hm = ballot(head);
         const uint32_t k = nh + popc(hm & lt_mask());
@@ -342,7 +343,7 @@ __device__ __forceinline__ uint32_t emit_doc(const HistParams &P, const HistDesc
     const uint32_t n_lv = R.n_lv;
     if (n_lv > D.c_lv) return ErrCapacity;
     uint32_t n_ent = 0, n_par = 0;
-    if (!emit_entries(D, B, S, O, n_lv, n_ent, n_par)) return ErrCapacity;
+    if (!emit_entries(D, B, S, O, n_lv, n_ent, n_par, P.keep_entries != 0)) return ErrCapacity;
     const uint32_t apieces = arun_pieces(D, B, S, O);
     if (apieces == NONE) return ErrCapacity;
     fence_agent();   // the pieces and the entry heads, before the passes that read them

@@ -48,6 +48,10 @@ struct HistParams {
     // emit launch: the final counts.
     DecodeResult *results;
     uint32_t n_docs, lds_entries;
+    // 1: an included base entry is never joined to its predecessor, so the output's entries are the
+    // base document's (clipped).  A walk over the output then visits what a walk over the base
+    // document's spans visits, in the same order (the merge requests, dtgpu_merge.cpp).
+    uint32_t keep_entries;
 };
 
 int launch_hist_mark(const HistParams &p, void *stream);

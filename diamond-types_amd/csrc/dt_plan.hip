@@ -1316,6 +1316,366 @@ __global__ __launch_bounds__(64) void walk_kernel(PlanParams Q) {
     }
 }
 
+// ---- plan_kernel_xf: iter_xf_operations_from(from, merging) over a projected history ------------
+//
+// The document is the projection of Hist(from u merging) (dt_history.hip, entries kept as the base
+// document's), the merged frontier is its tip.  build_xf_plan_from (dt_host.cpp) in the planner's
+// terms: with vF the version vector of `from`, entry e of chain c has its first
+// clamp(vF[c] - seq0, 0, len) LVs in Hist(from) -- its A part; the rest is its B part.
+//   phase A   the spanning-tree walk over the A parts from ROOT, then one move to `from`: replayed,
+//             not reported (PlanResult.xf_first = the first reported command);
+//   prefix    B parts in ascending LV order while the part's parents are the frontier
+//             (merge.rs:792-835): applied with no move;
+//   phase B   the spanning-tree walk over the B parts that are left, then the move to the tip.
+// A parent is consumed before phase B when it lies in an A part (pcnt <= vF[pch]) or below the
+// prefix's bound; phase B counts only the other parents.  The B part of an entry with an A part
+// has the one parent start - 1, consumed: it is a root of phase B, and no merge.
+struct XS {
+    uint32_t n_rep;      // reported LVs so far
+    uint32_t rep;        // commands pushed now are reported
+};
+// (vc clamped into the entry's seq range first, then the subtraction: no operand of it can wrap)
+DEV uint32_t a_len(uint32_t vc, uint32_t seq0, uint32_t len) {
+    const uint32_t hi = seq0 + len;
+    const uint32_t v = vc < seq0 ? seq0 : vc > hi ? hi : vc;
+    return v - seq0;
+}
+// vF of a chain chosen per lane (lane = chain in vF).  All 64 lanes must be active.
+DEV uint32_t vf_of(const VV<1> &vF, uint32_t ch) { return shfl(vF.v[0], ch & 63u); }
+DEV void xrow(const P &p, uint32_t e, VV<1> &row) {
+    const uint32_t l = lane();
+    row.v[0] = l < p.A ? p.prow[size_t(e) * p.row_stride + l] : 0u;
+}
+// The entry holding lv (lv < n_lv): the last entry whose start is <= lv.
+DEV uint32_t entry_of_lv(const P &p, uint32_t lv) {
+    uint32_t lo = 0, hi = p.ne;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (U(p.erec[size_t(mid) * EREC_HEAD + R_START]) <= lv) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+// Version vector of {lv}; chain and count of lv itself in c, n.
+DEV void xvv_at(P &p, uint32_t lv, VV<1> &row, uint32_t &c, uint32_t &n) {
+    const uint32_t e = entry_of_lv(p, lv);
+    const uint32_t rw = load_rec(p, e);
+    xrow(p, e, row);
+    c = R(rw, R_CHAIN);
+    n = R(rw, R_SEQ0) + (lv - R(rw, R_START)) + 1;
+    fold_entry<1>(p, R(rw, R_START), R(rw, R_END), lv, c, R(rw, R_SEQ0), row, false);
+}
+DEV void xmove(P &p, const VV<1> &from, const VV<1> &to, const VV<1> &dlo, const VV<1> &dhi) {
+    if (!vv_differ(from, to)) return;
+    const uint32_t t0 = p.nt;
+    emit_diff<1>(p, from, to, dlo, dhi, true);
+    if (!p.err && p.nt > t0) push_cmd(p, CMD_TOG, t0, p.nt - t0, 0);
+}
+// The entry's op runs clipped to the LVs [s, t) (truncate_tagged_span; XfPlanner::apply).
+DEV void xapply(P &p, XS &x, uint32_t op0, uint32_t nop, uint32_t s, uint32_t t) {
+    const uint32_t l = lane();
+    for (uint32_t j0 = 0; j0 < nop && !p.err; j0 += 64) {
+        const uint32_t j = j0 + l;
+        Cmd c{0, 0, 0, 0};
+        if (j < nop) c = p.opc[op0 + j];
+        const uint32_t lo = max(c.lv, s), hi = min(c.lv + c.len, t);
+        const bool inc = j < nop && lo < hi;
+        const u64 m = __ballot(inc);
+        const uint32_t cnt = uint32_t(__popcll(m));
+        if (uint64_t(p.nc) + cnt > p.ccap) { fail(p, PLAN_CMDS_FULL); return; }
+        if (inc && !p.count_only) {
+            const uint32_t k = lo - c.lv, mm = hi - lo;
+            const uint32_t pos = (c.op & 15u) == CMD_INS ? c.pos + k : (c.op & 16u) ? c.pos : c.pos + c.len - k - mm;
+            p.cmds[p.nc + uint32_t(__popcll(m & ((1ull << l) - 1ull)))] = Cmd{c.op, lo, mm, pos};
+        }
+        p.nc += cnt;
+        const uint32_t tot = rdl(scan_incl(inc ? hi - lo : 0u), 63);
+        if (x.rep) x.n_rep += tot;
+    }
+}
+// One of the two walks.  PB = false: the A parts from ROOT.  PB = true: the B parts that start
+// at or above `bound` (the first LV the prefix did not consume).  vf: the tracker's version.
+template <bool PB>
+DEV void xwalk(P &p, XS &x, uint32_t bound, VV<1> &vf, const VV<1> &vF, const VV<1> &dlo, const VV<1> &dhi) {
+    const uint32_t l = lane();
+    const uint32_t *H = p.erec;
+    uint32_t top = 0;
+    for (uint32_t c0 = 0; c0 < p.ne; c0 += 64) {
+        const uint32_t e = c0 + l;
+        const bool valid = e < p.ne;
+        const uint32_t *h = H + size_t(valid ? e : 0u) * EREC_HEAD;
+        const uint32_t st = h[R_START], len = h[R_END] - st, np = h[R_NP], ch = h[R_CHAIN], po = h[R_POFF];
+        const uint32_t vc = vf_of(vF, ch);
+        const uint32_t al = ch < p.A ? a_len(vc, h[R_SEQ0], len) : 0u;
+        uint32_t pend = np;
+        bool in = valid && al > 0, mg = np >= 2;
+        if (PB) {
+            in = valid && al < len && st + al >= bound;
+            // the parents that are not consumed yet (every lane steps together: vf_of)
+            const uint32_t cnt = in && al == 0 ? np : 0u;
+            uint32_t left = 0;
+            for (uint32_t j = 0; __ballot(j < cnt) != 0; j++) {
+                const bool on = j < cnt;
+                const uint32_t pc = on ? p.pch[po + j] : 0u;
+                const uint32_t vpc = vf_of(vF, pc);
+                if (on) {
+                    const bool done = (pc < p.A && p.pcnt[po + j] <= vpc) || p.par[po + j] < bound;
+                    left += done ? 0u : 1u;
+                }
+            }
+            if (al > 0) { pend = 0; mg = false; }
+            else pend = left;
+        }
+        // (an entry outside this walk: 0x7F without the merge bit, which no entry of the walk holds --
+        // a non-merge has at most one parent -- and which never reaches zero: it is never decremented)
+        if (valid) p.pending[e] = in ? uint8_t(min(pend, 0x7Fu) | (mg ? MERGE_BIT : 0)) : uint8_t(0x7F);
+    }
+    fence_wave();
+    for (int c = int((p.ne + 63) / 64) - 1; c >= 0; c--) {   // the roots, the first one on top
+        if (!charge(p)) break;
+        const uint32_t e = uint32_t(c) * 64 + (63 - l);
+        const bool root = e < p.ne && (p.pending[e] & 0x7F) == 0;
+        const u64 m = __ballot(root);
+        const uint32_t rank = uint32_t(__popcll(m & ((1ull << l) - 1ull)));
+        if (top + uint32_t(__popcll(m)) > PLAN_TODO_CAP) { fail(p, PLAN_TODO_FULL); break; }
+        if (root) p.todo[top + rank] = uint16_t(e);
+        top += uint32_t(__popcll(m));
+    }
+    fence_wave();
+    while (top > 0 && !p.err) {
+        if (!charge(p)) break;
+        const uint32_t idx = pick(p, top);
+        const uint32_t rw = load_rec(p, idx);
+        const uint32_t st = R(rw, R_START), en = R(rw, R_END), op0 = R(rw, R_OP0), nop = R(rw, R_NOP),
+                       ch0 = R(rw, R_CH0), nch = R(rw, R_NCH), chain = R(rw, R_CHAIN), seq0 = R(rw, R_SEQ0);
+        if (chain >= p.A || en <= st) { fail(p, PLAN_ERR_INTERNAL); break; }
+        const uint32_t al = a_len(rdl(vF.v[0], chain), seq0, en - st);
+        const uint32_t s = PB ? st + al : st, t = PB ? en : st + al;
+        if (s >= t) { fail(p, PLAN_ERR_INTERNAL); break; }
+        // the part's parents: the entry's, or (a B part behind an A part) the LV before it
+        VV<1> vp;
+        xrow(p, idx, vp);
+        if (l == chain) vp.v[0] = max(vp.v[0], seq0 + (s - st));
+        xmove(p, vf, vp, dlo, dhi);
+        if (p.err) break;
+        xapply(p, x, op0, nop, s, t);
+        if (p.err) break;
+        vf = vp;
+        if (l == chain) vf.v[0] = seq0 + (t - st);
+        // children whose last counted parent this part held (pushed in child index order)
+        for (uint32_t c = 0; c < nch; c += 64) {
+            bool ready = false;
+            const bool valid = c + l < nch;
+            const uint32_t chv = valid ? p.child[ch0 + c + l] : 0u;
+            const uint32_t *h = H + size_t(chv) * EREC_HEAD;
+            const uint32_t cst = h[R_START], cch = h[R_CHAIN];
+            const uint32_t cvc = vf_of(vF, cch);
+            const uint32_t cal = cch < p.A ? a_len(cvc, h[R_SEQ0], h[R_END] - cst) : 0u;
+            if (valid) {
+                bool dec = cal > 0;
+                if (PB) {   // counted iff the child has no A part and its parent here lies in this part
+                    dec = false;
+                    const uint32_t po = h[R_POFF], np = h[R_NP];
+                    for (uint32_t j = 0; j < np && cal == 0; j++) {
+                        const uint32_t pl = p.par[po + j];
+                        if (pl >= st && pl < en) { dec = pl >= s; break; }
+                    }
+                }
+                if (dec) {
+                    const uint8_t pd = uint8_t(p.pending[chv] - 1);
+                    p.pending[chv] = pd;
+                    ready = (pd & 0x7F) == 0;
+                }
+            }
+            const u64 m = __ballot(ready);
+            const uint32_t rank = uint32_t(__popcll(m & ((1ull << l) - 1ull)));
+            if (top + uint32_t(__popcll(m)) > PLAN_TODO_CAP) { fail(p, PLAN_TODO_FULL); break; }
+            if (ready) p.todo[top + rank] = uint16_t(chv);
+            top += uint32_t(__popcll(m));
+        }
+        fence_wave();
+    }
+}
+
+DEV void plan_doc_xf(P &p, XS &x, const uint32_t *from, uint32_t n_from, PlanResult *res) {
+    const uint32_t l = lane();
+    VV<1> vf, vF, dlo, dhi;
+    vv_zero(vf);
+    vv_zero(vF);
+    dlo.v[0] = l < p.A ? p.doff[l] : 0;
+    dhi.v[0] = l < p.A ? p.doff[l + 1] : 0;
+    {   // a parent count past the pending byte: as the whole-document planner
+        bool bad_np = false;
+        for (uint32_t e = l; e < p.ne; e += 64) bad_np |= p.erec[size_t(e) * EREC_HEAD + R_NP] > 0x7Fu;
+        if (__ballot(bad_np)) fail(p, PLAN_WIDE_MERGE);
+    }
+    // vF, and `from` reduced to a frontier (lane j: its j-th LV, ascending as given): an LV is
+    // dominated when another one's history reaches it on its chain.  Serial over the set, quadratic
+    // for the LVs that end their chain's part of it: the caller bounds the set (MERGE_MAX_FROM)
+    for (uint32_t j = 0; j < n_from && !p.err; j++) {
+        if (!charge(p)) break;
+        const uint32_t lv = U(from[j]);
+        if (lv >= p.n_lv) { fail(p, PLAN_ERR_INTERNAL); break; }
+        VV<1> t;
+        uint32_t c, n;
+        xvv_at(p, lv, t, c, n);
+        vv_max(vF, t);
+    }
+    uint32_t fr = 0, nfr = 0;
+    for (uint32_t j = 0; j < n_from && !p.err; j++) {
+        if (!charge(p)) break;
+        const uint32_t lv = U(from[j]);
+        VV<1> t;
+        uint32_t c, n;
+        xvv_at(p, lv, t, c, n);
+        bool dom = rdl(vF.v[0], c) > n;   // a later LV of its chain is in Hist(from)
+        for (uint32_t k = 0; k < n_from && !dom && !p.err; k++) {
+            if (!charge(p)) break;
+            const uint32_t lk = U(from[k]);
+            if (lk == lv) { dom = k < j; continue; }   // a repeat counts once
+            VV<1> tk;
+            uint32_t ck, nk;
+            xvv_at(p, lk, tk, ck, nk);
+            dom = rdl(tk.v[0], c) >= n;
+        }
+        if (!dom) {
+            if (nfr >= 64) { fail(p, PLAN_ERR_INTERNAL); break; }
+            if (l == nfr) fr = lv;
+            nfr++;
+        }
+    }
+    tk(p);
+    // phase A: Hist(from), then the tracker at `from`
+    x.rep = 0;
+    if (!p.err && n_from) xwalk<false>(p, x, 0, vf, vF, dlo, dhi);
+    if (!p.err) xmove(p, vf, vF, dlo, dhi);
+    vf = vF;
+    const uint32_t first = p.nc;
+    x.rep = 1;
+    // the fast-forward prefix: B parts in LV order while their parents are the frontier
+    uint32_t bound = p.n_lv;
+    bool single = false;   // the frontier is the one LV f (else: `from`, fr / nfr)
+    uint32_t f = 0;
+    for (uint32_t e = 0; e < p.ne && !p.err; e++) {
+        if (!charge(p)) break;
+        {   // skip, 64 at a time, the entries that lie in Hist(from) whole
+            const uint32_t k = e + l;
+            const uint32_t *h = p.erec + size_t(k < p.ne ? k : 0u) * EREC_HEAD;
+            const uint32_t len = h[R_END] - h[R_START], ch = h[R_CHAIN];
+            const uint32_t vc = vf_of(vF, ch);
+            const bool part = k < p.ne && (ch >= p.A || a_len(vc, h[R_SEQ0], len) < len);
+            const u64 m = __ballot(part);
+            if (!m) { e += 63; continue; }
+            e += ctz(m);
+        }
+        const uint32_t rw = load_rec(p, e);
+        const uint32_t st = R(rw, R_START), en = R(rw, R_END), chain = R(rw, R_CHAIN), seq0 = R(rw, R_SEQ0),
+                       np = R(rw, R_NP), po = R(rw, R_POFF);
+        if (chain >= p.A) { fail(p, PLAN_ERR_INTERNAL); break; }
+        const uint32_t al = a_len(rdl(vF.v[0], chain), seq0, en - st);
+        if (al == en - st) continue;   // all of it in Hist(from)
+        const uint32_t s = st + al;
+        bool same;
+        if (al > 0) {
+            same = single ? f == s - 1 : (nfr == 1 && rdl(fr, 0) == s - 1);
+        } else if (single) {
+            same = np == 1 && R(rw, R_PAR0) == f;
+        } else {   // the parents and `from`: two reduced frontiers of equal size, one inside the other
+            same = np == nfr;
+            for (uint32_t j = 0; j < np && same; j++) {
+                const uint32_t pl = U(p.par[po + j]);
+                same = __ballot(l < nfr && fr == pl) != 0;
+            }
+        }
+        if (!same) { bound = s; break; }
+        xapply(p, x, R(rw, R_OP0), R(rw, R_NOP), s, en);
+        if (l == chain) vf.v[0] = seq0 + (en - st);
+        single = true;
+        f = en - 1;
+    }
+    // phase B: what is left, then the merged version
+    if (!p.err && bound < p.n_lv) xwalk<true>(p, x, bound, vf, vF, dlo, dhi);
+    if (!p.err) {
+        VV<1> vt;
+        vv_zero(vt);
+        for (uint32_t j = 0; j < p.ntip && !p.err; j++) {
+            const uint32_t lv = U(p.tip[2 * j]);
+            if (lv >= p.n_lv) { fail(p, PLAN_ERR_INTERNAL); break; }
+            VV<1> t;
+            uint32_t c, n;
+            xvv_at(p, lv, t, c, n);
+            vv_max(vt, t);
+        }
+        if (!p.err && vv_differ(vf, vt)) {
+            const uint32_t adv0 = p.n_adv;
+            xmove(p, vf, vt, dlo, dhi);
+            res->n_tip = uint32_t(p.n_adv - adv0);
+            p.n_adv = adv0;
+        }
+    }
+    if (l == 0) {
+        for (int i = 0; i < 6; i++) res->prof[i] = p.prof ? g_pc[i] : 0;
+        res->status = p.err;
+        res->ncmd = p.nc;
+        res->ntlist = p.nt;
+        res->n_retreat = p.n_ret;
+        res->n_advance = p.n_adv;
+        res->xf_first = first;
+        res->n_xf = x.n_rep;
+    }
+}
+
+__global__ __launch_bounds__(64) void plan_kernel_xf(PlanParams Q) {
+    extern __shared__ __attribute__((aligned(16))) uint16_t lds16[];
+    if (blockIdx.x >= Q.n_docs) return;
+    const uint32_t d = U(Q.doc_list ? Q.doc_list[blockIdx.x] : blockIdx.x);
+    const PlanDesc pd = Q.docs[d];
+    PlanResult *res = Q.results + d;
+    if (pd.skip) return;
+    const uint32_t A = U(pd.n_agents);
+    P p;
+    p.erec = Q.erec + pd.erec_off;
+    p.par = Q.par + pd.par_off;
+    p.pent = Q.pent + pd.par_off;
+    p.pch = Q.pch + pd.par_off;
+    p.pcnt = Q.pcnt + pd.par_off;
+    p.child = Q.child + pd.child_off;
+    p.opc = Q.opc + pd.op_off;
+    p.doff = Q.doff + pd.doff_off;
+    p.dense = Q.dense + pd.dense_off;
+    p.tip = Q.tip + pd.tip_off * 2;
+    p.ne = U(pd.ne);
+    p.A = A;
+    p.ntip = U(pd.ntip);
+    p.n_lv = U(pd.n_lv);
+    // LDS: the todo stack, the pending bytes
+    XS x;
+    x.n_rep = 0;
+    x.rep = 0;
+    p.todo = lds16;
+    p.pending = reinterpret_cast<uint8_t *>(lds16 + PLAN_TODO_CAP);
+    p.base = nullptr;
+    p.prow = Q.prow + pd.prow_off;
+    p.order = nullptr;
+    p.walk = nullptr;
+    p.row_stride = pd.row_stride;
+    p.cmds = Q.cmds + pd.cmd_off;
+    p.tlist = Q.tlist + pd.tlist_off;
+    p.count_only = Q.count_only;
+    p.ccap = Q.count_only ? 0xFFFFFFFFu : U(pd.ccap);
+    p.tcap = Q.count_only ? 0xFFFFFFFFu : U(pd.tcap);
+    p.nc = p.nt = p.err = 0;
+    p.steps = 0;
+    p.limit = uint32_t(min<uint64_t>(2048ull * (uint64_t(p.ne) + 16) + 4ull * pd.n_lv + 4ull * uint64_t(pd.n_from) * pd.n_from + (1u << 20), 0xFFFFFFF0ull));
+    p.n_ret = p.n_adv = 0;
+    p.prof = Q.prof;
+    res->n_tip = 0;
+    if (p.ne > Q.lds_entries || A > 64 || p.ne == 0) {
+        if (lane() == 0) res->status = PLAN_ERR_INTERNAL;
+        return;
+    }
+    plan_doc_xf(p, x, Q.xf_from + pd.xf_off, U(pd.n_from), res);
+}
+
 }  // namespace pdev
 
 int launch_walk(const PlanParams &q, void *stream, bool csr) {
@@ -1339,6 +1699,10 @@ int launch_plan(const PlanParams &q, void *stream, bool walk) {
     if (!q.n_docs) return OK;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const size_t lds = 2 * size_t(PLAN_TODO_CAP) + ((size_t(q.lds_entries) + 15) & ~size_t(15));   // todo + pending
+    if (q.xf) {   // merge requests over projected histories
+        hipLaunchKernelGGL(pdev::plan_kernel_xf, dim3(q.n_docs), dim3(64), lds, s, q);
+        return launch_error() == hipSuccess ? OK : ErrHip;
+    }
     if (walk && q.split && q.walk && launch_walk(q, stream, false)) return ErrHip;
     if (q.split) hipLaunchKernelGGL(pdev::plan_kernel_1<true>, dim3(q.n_docs), dim3(64), lds, s, q);
     else hipLaunchKernelGGL(pdev::plan_kernel_1<false>, dim3(q.n_docs), dim3(64), lds, s, q);

@@ -19,6 +19,7 @@
 #include "dt_decoded.hpp"
 #include "dt_history.hpp"
 #include "dt_host.hpp"
+#include "dt_merge.hpp"
 #include "dt_patch.hpp"
 #include "dt_request.hpp"
 
@@ -528,6 +529,11 @@ dtgpu_status dtgpu_decode_add_result(const dtgpu_decoded *M, size_t i, uint64_t 
 // bounds for the run arrays), the arenas are laid out from its counts and the emit launch fills them.
 dtgpu_status dtgpu_decode_history(const dtgpu_decoded *B, const uint32_t *doc, const uint64_t *versions,
                                   const size_t *version_off, size_t n, float *ms, dtgpu_decoded **out) {
+    return dtgpu::decode_history(B, doc, versions, version_off, n, ms, out, nullptr);
+}
+extern "C++" dtgpu_status dtgpu::decode_history(const dtgpu_decoded *B, const uint32_t *doc, const uint64_t *versions,
+                                                const size_t *version_off, size_t n, float *ms, dtgpu_decoded **out,
+                                                HistKeep *keep) {
     if (!B || !out || (n && (!doc || !version_off))) return DTGPU_ERR_ARG;
     if (!B->merged && !B->ran) return DTGPU_ERR_ARG;   // not decoded yet
     for (size_t i = 0; i < n; i++)
@@ -597,6 +603,7 @@ dtgpu_status dtgpu_decode_history(const dtgpu_decoded *B, const uint32_t *doc, c
     H.b_poff = B->poff.p; H.b_par = B->par.p; H.b_cbyte = B->cbyte.p; H.b_agents = B->agents.p;
     H.req = d_req.p; H.scr = d_scr.p; H.o_ver = M->ver.p; H.o_front = M->hfr.p;
     H.docs = d_hd.p; H.results = M->d_res.p; H.n_docs = uint32_t(n); H.lds_entries = lds_entries;
+    H.keep_entries = keep ? 1u : 0u;
     CK(hipEventRecord(M->ev0, s));
     if (launch_hist_mark(H, s)) return DTGPU_ERR_HIP;
     CK(hipEventRecord(M->ev1, s));
@@ -654,6 +661,10 @@ dtgpu_status dtgpu_decode_history(const dtgpu_decoded *B, const uint32_t *doc, c
         r.prof[1] = uint32_t(t0 * 1000.f);   // the launches' microseconds, with the mark form in prof[0]
         r.prof[2] = uint32_t(t1 * 1000.f);
         M->add_status[i] = r.status;
+    }
+    if (keep) {
+        std::swap(keep->scr.p, d_scr.p); std::swap(keep->scr.n, d_scr.n);
+        std::swap(keep->hd.p, d_hd.p); std::swap(keep->hd.n, d_hd.n);
     }
     *out = guard.release();
     return DTGPU_OK;

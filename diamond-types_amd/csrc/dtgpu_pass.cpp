@@ -4,6 +4,7 @@
 #include <cstring>
 
 #include "dt_batch.hpp"
+#include "dt_merge.hpp"
 
 using namespace dtgpu;
 
@@ -233,7 +234,9 @@ int launch_tracker(dtgpu_batch *B, hipStream_t s, const PassMarks &m) {
 int launch_pass(dtgpu_batch *B, hipStream_t s, const PassMarks &m = {}) {
     if (B->pass_mark && launch_pass_mark(s)) return ErrHip;
     if (mark(m.start, s)) return ErrHip;
-    if (B->xf_mode) {   // host plans (n_gpu_planned is 0), every document on the HBM tier
+    if (B->xf_mode) {   // every document on the HBM tier; host plans (n_gpu_planned is 0), or a merge
+                        // batch (device-staged): prep, then plan_kernel_xf
+        if (B->dec && launch_prep(B->prep, s)) return ErrHip;
         if (mark(m.prepped, s)) return ErrHip;
         if (B->n_gpu_planned && launch_plan(B->plan, s) != OK) return ErrHip;
         return mark(m.planned, s) ? ErrHip : launch_replay_xf(B->large, s);
@@ -452,6 +455,16 @@ dtgpu_status dtgpu_batch_run_timed(dtgpu_batch *B, float *ms) {
     B->last_plan_ms = tp;
     B->last_replay_ms = t - tp - tq;
     if (ms) *ms = t;
+    return DTGPU_OK;
+}
+extern "C++" dtgpu_status dtgpu::run_xf_pass(dtgpu_batch *B, float ms[3]) {
+    if (!B || !B->xf_mode || !B->dec) return DTGPU_ERR_ARG;
+    float t = 0;
+    const dtgpu_status st = dtgpu_batch_run_timed(B, &t);
+    if (st != DTGPU_OK) return st;
+    ms[0] = t - B->last_plan_ms - B->last_replay_ms;
+    ms[1] = B->last_plan_ms;
+    ms[2] = B->last_replay_ms;
     return DTGPU_OK;
 }
 dtgpu_status dtgpu_batch_sync(dtgpu_batch *B) {

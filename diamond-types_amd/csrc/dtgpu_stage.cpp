@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "dt_batch.hpp"
+#include "dt_merge.hpp"
 
 #define CK(x) do { if (DTGPU_HIP_FAILED(x)) return DTGPU_ERR_HIP; } while (0)
 
@@ -797,7 +798,11 @@ dtgpu_status stage(std::vector<Prepared> &prep, const dtgpu_batch_opts *opts, dt
 // replay layout.  The host only reads back per-document counts to size the arenas.  Documents
 // the device path hands back (decoder or prep limits) get status DTGPU_DECODE_DEFER.
 // `dec` is a decoded handle (dtgpu_decode_create: decoded here; dtgpu_decode_add: already merged).
-dtgpu_status stage_device(dtgpu_decoded *dec, const dtgpu_batch_opts *opts, dtgpu_batch **out) {
+//
+// xf: the merge form (dtgpu_decode_xf_from).  Every document is the projected history of a merge
+// request; plan_kernel_xf plans it from the request's `from`, and every document replays on the
+// HBM tier in transformed-ops mode: no fast-forward layout, no segments, no split or late pipeline.
+dtgpu_status stage_device(dtgpu_decoded *dec, const dtgpu_batch_opts *opts, dtgpu_batch **out, XfStage *xf) {
     auto B = std::make_unique<dtgpu_batch>();
     B->cfg = settings_for(opts);
     B->device = dec->device;
@@ -832,6 +837,7 @@ dtgpu_status stage_device(dtgpu_decoded *dec, const dtgpu_batch_opts *opts, dtgp
         uint32_t st = r.status;
         if (st == OK && !r.content_complete) st = ErrCheckout;   // content.unwrap() in apply_to
         if (st == OK && (r.n_lv >= MAX_PLAN_LV || r.n_entries > PLAN_MAX_LDS_ENTRIES)) st = DECODE_DEFER;
+        if (st == OK && xf && xf->skip[i]) st = DECODE_DEFER;   // answered by the caller
         B->host_status[i] = st;
         B->n_lv[i] = r.n_lv;
         B->n_runs[i] = r.n_ops;
@@ -902,6 +908,7 @@ dtgpu_status stage_device(dtgpu_decoded *dec, const dtgpu_batch_opts *opts, dtgp
         q.poff_off = r.d_poff;
         q.row_stride = PREP_MAX_CHAINS;
         q.ne = r.ne; q.n_agents = prr[i].n_chains; q.n_aruns = r.n_aruns; q.ntip = r.n_ver; q.n_lv = r.n_lv;
+        if (xf) { q.xf_off = xf->from_off[i]; q.n_from = uint32_t(xf->from_off[i + 1] - xf->from_off[i]); }
         base_total += uint64_t(r.ne) * std::max<uint32_t>(prr[i].n_chains, 1);
         lds_entries = std::max<uint32_t>(lds_entries, r.ne);
         max_agents = std::max<uint32_t>(max_agents, prr[i].n_chains);
@@ -911,6 +918,7 @@ dtgpu_status stage_device(dtgpu_decoded *dec, const dtgpu_batch_opts *opts, dtgp
     q.prow = B->pr_rows.p;
     q.coff = B->pr_scr.p;
     q.poff = Dd.poff.p;
+    if (xf) { q.xf = 1; q.xf_from = xf->d_from; }
     std::vector<PlanResult> pres;
     std::vector<uint32_t> wres;
     if (size_plans(*B, pdesc, o_erec, lds_entries, max_agents, pres, &wres) != DTGPU_OK) return DTGPU_ERR_HIP;
@@ -918,7 +926,7 @@ dtgpu_status stage_device(dtgpu_decoded *dec, const dtgpu_batch_opts *opts, dtgp
     // here (plus slack), not PLAN_TODO_CAP -- the walk kernel's LDS then leaves room for the
     // chain decomposition's waves beside it.  (A deeper walk would fail its document visibly,
     // PLAN_TODO_FULL; the walk is deterministic, so none does.)
-    if (q.walk && q.split) {
+    if (q.walk && q.split && !xf) {
         uint32_t deep = 0;
         for (size_t i = 0; i < n; i++)
             if (!pdesc[i].skip && pres[i].status == PLAN_OK) deep = std::max(deep, wres[2 * i] >> 16);
@@ -938,13 +946,14 @@ dtgpu_status stage_device(dtgpu_decoded *dec, const dtgpu_batch_opts *opts, dtgp
         const DecodeDesc &dd = Dd.desc[i];
         const DocFacts f = facts_of(r, prr[i]);
         plan_slots(*B, d, pdesc[i], pres[i], T);
+        if (xf) { xf->xf_first[i] = pres[i].xf_first; xf->n_xf[i] = pres[i].n_xf; }
         describe(d, f);
         d.lv_off = dd.lv_off;                 // per-LV arenas share the decoder's LV numbering
         d.pc_off = dd.lv_off;
         d.content_off = dd.content_off;       // inserted text read in place
         d.arun_off = pd[i].o_arun * 4;
         d.n_aruns = r.n_aruns;
-        if (B->cfg.ff && f.linear) {
+        if (!xf && B->cfg.ff && f.linear) {
             layout_ff_doc(*B, i, f, T);
             B->total_lv += r.n_lv;
             continue;
@@ -954,12 +963,12 @@ dtgpu_status stage_device(dtgpu_decoded *dec, const dtgpu_batch_opts *opts, dtgp
         // ErrCapacity there.  A known inconsistency, kept as it is.
         if (over_block_limit(f.n_ins)) { B->host_status[i] = ErrCapacity; pdesc[i].skip = 1; continue; }
         B->total_lv += r.n_lv;
-        seg_tier[i] = layout_tracker_doc(*B, i, f, false, T);
+        seg_tier[i] = layout_tracker_doc(*B, i, f, xf != nullptr, T);
     }
     T.lv = Dd.cbyte.n;
     // cut replay: long documents' later LV ranges as documents of their own
     T.pc = T.lv;
-    {
+    if (!xf) {
         SegSettings sc = seg_settings(B->cfg);
         const std::vector<uint32_t> cand = seg_candidates(n, sc, B->n_cu, B->cfg.seg_fair, [&](size_t k) { return seg_tier[k] != -2 ? Dd.res[k].n_ops : 0u; });
         std::vector<uint8_t> late = late_documents(*B, sc, [&](size_t k) { return Dd.res[k].n_ops; });
@@ -1073,6 +1082,12 @@ dtgpu_status stage_device(dtgpu_decoded *dec, const dtgpu_batch_opts *opts, dtgp
         c.n_groups = uint32_t(B->seg_groups.size());
         if (!B->ev_cut) CK(hipEventCreateWithFlags(&B->ev_cut, hipEventDisableTiming));
     }
+    if (xf) {   // the transformed-ops replay's arenas, as stage() allocates them for its xf batches
+        CK(B->d_mup.alloc(T.blk));
+        CK(B->d_tup.alloc(T.blk + 2 * n));
+        CK(B->d_xf.alloc(T.lv));
+        B->xf_mode = true;
+    }
     CK(hipStreamSynchronize(s));
     stage_prof("stage: arenas + uploads");
     if (set_tier_params(*B, Dd.cbyte.p, Dd.content.p) != DTGPU_OK) return DTGPU_ERR_HIP;
@@ -1082,7 +1097,7 @@ dtgpu_status stage_device(dtgpu_decoded *dec, const dtgpu_batch_opts *opts, dtgp
     // start as soon as their own plans are done).  The tier: the critical documents' (DOC_CRITICAL,
     // the batch's longest replays), else the biggest non-empty one.  Its segment documents'
     // documents are planned there too (the main pipeline's replay waits for those plans).
-    if (B->cfg.split) {
+    if (B->cfg.split && !xf) {
         int tb = -1;
         for (int t = kLdsTiers - 1; t >= 1 && tb < 0; t--)
             for (uint32_t d : B->tier_list[t])

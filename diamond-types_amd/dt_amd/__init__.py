@@ -256,6 +256,14 @@ def lib():
     L.dtgpu_intersect_remainder.argtypes = [vp, sz, pu64, sz, psz]
     L.dtgpu_intersect_profile.argtypes = [vp, sz, pu32]
     L.dtgpu_intersect_free.argtypes = [vp]
+    L.dtgpu_decode_xf_from.argtypes = [vp, pu32, pu64, psz, pu64, psz, sz, pf, ctypes.POINTER(vp)]
+    L.dtgpu_merges_size.argtypes = [vp]
+    L.dtgpu_merges_size.restype = sz
+    L.dtgpu_merges_result.argtypes = [vp, sz, pu64, sz, psz]
+    L.dtgpu_merges_ops.argtypes = [vp, sz, pu32, sz, psz]
+    L.dtgpu_merges_text.argtypes = [vp, sz, ctypes.c_char_p, sz, psz]
+    L.dtgpu_merges_profile.argtypes = [vp, sz, pu32]
+    L.dtgpu_merges_free.argtypes = [vp]
     L.dtgpu_graph_queries.argtypes = [ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(sz), sz,
                                       ctypes.POINTER(GraphQuery), sz, ctypes.POINTER(ctypes.c_int64), sz,
                                       ctypes.POINTER(ctypes.c_int64), sz,
@@ -355,6 +363,58 @@ def _read_summary(call):
     _check(call(names, nb, name_off, range_off, ne, ranges, nr, sizes))
     return [(names.raw[name_off[e]:name_off[e + 1]].decode(errors="surrogateescape"),
              [(ranges[2 * k], ranges[2 * k + 1]) for k in range(range_off[e], range_off[e + 1])]) for e in range(ne)]
+
+
+def merge_xf_runs(ops, content, char_offsets, stream):
+    """The run-merging of iter_xf_operations over a decoded oplog's arrays (`ops` as export("ops"),
+    the inserted `content` bytes, the per-LV `char_offsets`) and a stream of (lv, pos | None) in
+    application order: yields (range(lv, lv+len), op).  Consecutive LVs of one op run are merged
+    when they form one reference-style op: an insert at consecutive positions, a forward delete at
+    one position, a backspace run at descending positions (reported at its lowest position, like
+    BaseMoved)."""
+    ops = ops.reshape(-1, 4)
+    coff = char_offsets
+    run_of = {}
+    for r, (lv, ln, _pos, kf) in enumerate(ops):
+        for k in range(int(ln)):
+            run_of[int(lv) + k] = (r, int(kf) & 1)
+
+    def char(v):
+        b = coff[v]
+        n = 1 if content[b] < 0x80 else 2 if content[b] < 0xE0 else 3 if content[b] < 0xF0 else 4
+        return content[b:b + n].decode("utf-8")
+
+    cur = None   # [start_lv, end_lv, run, kind, first_pos, last_pos, text, step]
+    for lv, x in stream:
+        r, kind = run_of[lv]
+        if cur is not None and lv == cur[1] and r == cur[2]:
+            if x is None and cur[3] is None:
+                cur[1] += 1
+                continue
+            if x is not None and cur[3] == kind:
+                step = x - cur[5]
+                want = {0: (1,), 1: (0, -1)}[kind] if cur[7] is None else (cur[7],)
+                if step in want and (kind == 0 or cur[1] - cur[0] == 1 or step == cur[7]):
+                    cur[1] += 1
+                    cur[5] = x
+                    cur[7] = step
+                    if kind == 0:
+                        cur[6] += char(lv)
+                    continue
+        if cur is not None:
+            yield _xf_item(cur)
+        cur = [lv, lv + 1, r, None if x is None else kind, x, x, char(lv) if (x is not None and kind == 0) else "", None]
+    if cur is not None:
+        yield _xf_item(cur)
+
+
+def _xf_item(cur):
+    rng = range(cur[0], cur[1])
+    if cur[3] is None:
+        return rng, None
+    if cur[3] == 0:
+        return rng, ("ins", cur[4], cur[6])
+    return rng, ("del", min(cur[4], cur[5]), cur[1] - cur[0])
 
 
 def text_hash(data: bytes) -> int:
@@ -619,53 +679,10 @@ class ListOpLog:
     def iter_xf_operations(self, frm=None, merging=None):
         """ListOpLog::iter_xf_operations() (src/list/merge.rs:40-48): yields (range(lv, lv+len),
         op) with op = ("ins", pos, text) / ("del", pos, len) / None (DeleteAlreadyHappened).
-        Consecutive LVs of one op run are merged when they form one reference-style op: an
-        insert at consecutive positions, a forward delete at one position, a backspace run at
-        descending positions (reported at its lowest position, like BaseMoved)."""
-        ops = self.export("ops").reshape(-1, 4)
-        content = self.ins_content()
-        coff = self.char_offsets()
-        run_of = {}
-        for r, (lv, ln, _pos, kf) in enumerate(ops):
-            for k in range(int(ln)):
-                run_of[int(lv) + k] = (r, int(kf) & 1)
-
-        def char(v):
-            b = coff[v]
-            n = 1 if content[b] < 0x80 else 2 if content[b] < 0xE0 else 3 if content[b] < 0xF0 else 4
-            return content[b:b + n].decode("utf-8")
-
-        cur = None   # [start_lv, end_lv, run, kind, first_pos, last_pos, text, step]
-        for lv, x in self.xf_operations_lv(frm, merging):
-            r, kind = run_of[lv]
-            if cur is not None and lv == cur[1] and r == cur[2]:
-                if x is None and cur[3] is None:
-                    cur[1] += 1
-                    continue
-                if x is not None and cur[3] == kind:
-                    step = x - cur[5]
-                    want = {0: (1,), 1: (0, -1)}[kind] if cur[7] is None else (cur[7],)
-                    if step in want and (kind == 0 or cur[1] - cur[0] == 1 or step == cur[7]):
-                        cur[1] += 1
-                        cur[5] = x
-                        cur[7] = step
-                        if kind == 0:
-                            cur[6] += char(lv)
-                        continue
-            if cur is not None:
-                yield self._xf_item(cur)
-            cur = [lv, lv + 1, r, None if x is None else kind, x, x, char(lv) if (x is not None and kind == 0) else "", None]
-        if cur is not None:
-            yield self._xf_item(cur)
-
-    @staticmethod
-    def _xf_item(cur):
-        rng = range(cur[0], cur[1])
-        if cur[3] is None:
-            return rng, None
-        if cur[3] == 0:
-            return rng, ("ins", cur[4], cur[6])
-        return rng, ("del", min(cur[4], cur[5]), cur[1] - cur[0])
+        Consecutive LVs of one op run are merged when they form one reference-style op
+        (merge_xf_runs)."""
+        return merge_xf_runs(self.export("ops"), self.ins_content(), self.char_offsets(),
+                             self.xf_operations_lv(frm, merging))
 
     def encode(self, opts=None) -> bytes:
         """ListOpLog::encode(opts) (src/list/encoding/encode_oplog.rs:745-747); opts defaults to
@@ -1189,6 +1206,45 @@ class DecodeBatch:
             out[i] = ListBranch(b.text(k), fronts[k])
         return out
 
+    def xf_operations_from(self, docs, frm, merging):
+        """ListOpLog::iter_xf_operations_from(frm[i], merging[i]) of document docs[i] for a whole
+        batch, planned and replayed on the GPU (dtgpu_decode_xf_from): both are any sets of the
+        document's LVs ([] is ROOT); documents may repeat.  Returns a MergeBatch."""
+        n = len(docs)
+        if len(frm) != n or len(merging) != n:
+            raise ValueError("one from and one merging version per document index")
+
+        def csr(vs):
+            flat, off = [], [0]
+            for v in vs:
+                flat.extend(int(x) for x in v)
+                off.append(len(flat))
+            return _u64s(flat)[0], (ctypes.c_size_t * (n + 1))(*off)
+
+        pa, oa = csr(frm)
+        pb, ob = csr(merging)
+        d = (ctypes.c_uint32 * max(n, 1))(*[int(x) for x in docs])
+        ms, h = ctypes.c_float(), ctypes.c_void_p()
+        _check(lib().dtgpu_decode_xf_from(self._h, d, pa, oa, pb, ob, n, ctypes.byref(ms), ctypes.byref(h)))
+        return MergeBatch(h, n, ms.value, self, [int(x) for x in docs])
+
+    def merge(self, docs, branches, merging):
+        """ListBranch::merge for a batch: branches[i] is a ListBranch of document docs[i], taken from
+        its version to find_dominators_2(version, merging[i]).  A branch whose request failed is
+        left as it was; ParseError for the first such request is raised after the others are
+        updated."""
+        m = self.xf_operations_from(docs, [b.version for b in branches], merging)
+        bad = 0
+        for i, b in enumerate(branches):
+            st = m.status(i)
+            if st:
+                bad = bad or st
+                continue
+            b._content = m.content_bytes(i)
+            b.version = m.version(i)
+        _check(bad)
+        return m
+
     def checkout_batch(self):
         """A device-staged checkout Batch over these decoded (or merged) oplogs; consumes this
         handle (dtgpu_batch_create_decoded)."""
@@ -1253,6 +1309,75 @@ class PatchBatch:
         buf = ctypes.create_string_buffer(max(1, n.value))
         _check(lib().dtgpu_patches_get(self._h, i, buf, n.value, ctypes.byref(n)))
         return buf.raw[:n.value]
+
+
+class MergeBatch:
+    """The merges of one DecodeBatch.xf_operations_from call (dtgpu_merges): per request the merged
+    version, the transformed operations and the merged content."""
+
+    def __init__(self, handle, n, last_ms, base, docs):
+        self._h, self.n, self.last_ms, self._base, self._docs = handle, n, last_ms, base, docs
+        self._arrays = {}
+
+    def __len__(self):
+        return self.n
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            lib().dtgpu_merges_free(h)
+            self._h = None
+
+    def _result(self, i):
+        k = ctypes.c_size_t()
+        buf = (ctypes.c_uint64 * 64)()
+        st = lib().dtgpu_merges_result(self._h, i, buf, 64, ctypes.byref(k))
+        return st, list(buf[:k.value])
+
+    def status(self, i) -> int:
+        return self._result(i)[0]
+
+    def version(self, i):
+        """find_dominators_2(from, merging) in the base document's LVs, ascending."""
+        st, f = self._result(i)
+        _check(st)
+        return f
+
+    def xf_operations_lv(self, i):
+        """[(lv, pos or None)] in application order: ListOpLog.xf_operations_lv(frm, merging)."""
+        k = ctypes.c_size_t()
+        _check(lib().dtgpu_merges_ops(self._h, i, None, 0, ctypes.byref(k)))
+        n = k.value
+        buf = (ctypes.c_uint32 * max(2, 2 * n))()
+        _check(lib().dtgpu_merges_ops(self._h, i, buf, n, ctypes.byref(k)))
+        import numpy as np
+        a = np.frombuffer(buf, dtype=np.uint32, count=2 * n).reshape(-1, 2).tolist()
+        return [(lv, None if x == 0xFFFFFFFF else x) for lv, x in a]
+
+    def iter_xf_operations(self, i):
+        """What ListOpLog.iter_xf_operations(frm, merging) yields, from the resident document's
+        arrays (DecodeBatch.export)."""
+        d = self._docs[i]
+        if d not in self._arrays:
+            self._arrays[d] = (self._base.export(d, "ops"), bytes(self._base.export(d, "content")),
+                               self._base.export(d, "char_offsets"))
+        ops, content, coff = self._arrays[d]
+        return merge_xf_runs(ops, content, coff, self.xf_operations_lv(i))
+
+    def content_bytes(self, i) -> bytes:
+        """The branch's content after the merge: the checkout at version(i)."""
+        n = ctypes.c_size_t()
+        _check(lib().dtgpu_merges_text(self._h, i, None, 0, ctypes.byref(n)))
+        buf = ctypes.create_string_buffer(max(1, n.value))
+        _check(lib().dtgpu_merges_text(self._h, i, buf, n.value, ctypes.byref(n)))
+        return buf.raw[:n.value]
+
+    def profile(self, i):
+        """dtgpu_merges_profile: the batch's us in mark + projection, prep, plan, replay, LV
+        translation; then request i's commands, first reported command, reported LVs."""
+        out = (ctypes.c_uint32 * 8)()
+        _check(lib().dtgpu_merges_profile(self._h, i, out))
+        return list(out)
 
 
 class IntersectBatch:

@@ -589,6 +589,47 @@ dtgpu_status dtgpu_decode_encode_from_summaries(const dtgpu_decoded *base, const
 dtgpu_status dtgpu_decode_summarize(const dtgpu_decoded *base, size_t i, uint8_t *names, size_t names_cap,
                                     size_t *name_off, size_t *range_off, size_t entry_cap, uint64_t *ranges,
                                     size_t range_cap, size_t sizes[3]);
+/* ListOpLog::iter_xf_operations_from(from, merging) and ListBranch::merge (src/list/merge.rs:24-95)
+ * for a batch of resident documents, planned and replayed on the GPU.  Request i is document
+ * docs[i] of `base` (any handle dtgpu_decode_encode_from accepts; unchanged; documents may repeat,
+ * in any order): the version from[from_off[i] .. from_off[i + 1]) is taken to
+ * merging[merging_off[i] .. merging_off[i + 1]).  Both are any sets of the document's LVs, reduced
+ * to frontiers as dtgpu_xf_operations_from reduces them; empty is ROOT.  Every request's
+ * Hist(from u merging) is projected into an oplog of its own (dtgpu_decode_history's kernels), prep
+ * and plan_kernel_xf (dt_plan.hip) plan it on the device -- Hist(from) first, replayed and not
+ * reported, then the new operations in the reference's order -- and the transformed-ops replay
+ * runs it.  Per-request status: the base document's own when not 0; DTGPU_ERR_ARG for an LV
+ * outside the document; DTGPU_DECODE_DEFER when the device planner declines the request (more than
+ * 64 causal chains, more graph entries than the planner's LDS holds, a full ready stack, a merge of
+ * more than 127 parents, a reduced frontier wider than 64, a `from` of more than 256 distinct LVs:
+ * the planner reduces it on one wave); the replay's own statuses.  A failed
+ * request never fails the batch and has no frontier, no records and no text.  *kernel_ms = the
+ * device time of the pass's kernels (mark + projection, LV translation, prep, plan, replay).  Not in
+ * it: staging's own launches, which size the pass -- prep once more and plan_kernel_xf in its
+ * count-only mode -- so prep and the planner run twice per call and the first run is part of the
+ * call's wall clock only. */
+typedef struct dtgpu_merges dtgpu_merges;
+dtgpu_status dtgpu_decode_xf_from(const dtgpu_decoded *base, const uint32_t *docs, const uint64_t *from,
+                                  const size_t *from_off, const uint64_t *merging, const size_t *merging_off, size_t n,
+                                  float *kernel_ms, dtgpu_merges **out);
+size_t dtgpu_merges_size(const dtgpu_merges *m);
+/* Request i's status and the merged version, find_dominators_2(from, merging), in the base
+ * document's LVs, ascending: writes min(len, cap) LVs and the length. */
+dtgpu_status dtgpu_merges_result(const dtgpu_merges *m, size_t i, uint64_t *frontier, size_t cap, size_t *n_frontier);
+/* Request i's transformed operations: records {lv, pos} (two u32 each) in application order, pos =
+ * 0xFFFFFFFF for DeleteAlreadyHappened, LVs in the base document's numbering -- the records
+ * dtgpu_xf_operations_from writes for the same oplog and arguments: only the operations of
+ * Hist(merging) - Hist(from).  out == NULL: the count in *n_out; DTGPU_ERR_ARG when cap is too
+ * small.  Returns the request's status. */
+dtgpu_status dtgpu_merges_ops(const dtgpu_merges *m, size_t i, uint32_t *out, size_t cap, size_t *n_out);
+/* The branch's content after the merge (the checkout at the merged version), with
+ * dtgpu_batch_text's protocol. */
+dtgpu_status dtgpu_merges_text(const dtgpu_merges *m, size_t i, uint8_t *out, size_t cap, size_t *out_len);
+/* Where the pass's device time went (as *kernel_ms: without staging's sizing launches), in us
+ * (whole batch): out[0] = mark + projection, out[1] = prep, out[2] = plan, out[3] = replay, out[4] = the LV translation kernels; out[5] = request i's
+ * commands, out[6] = its first reported command, out[7] = its reported LVs. */
+dtgpu_status dtgpu_merges_profile(const dtgpu_merges *m, size_t i, uint32_t out[8]);
+void dtgpu_merges_free(dtgpu_merges *m);
 /* A device-staged checkout batch over a decoded handle (consumed, also on failure): decoded here
  * unless it already holds merged oplogs; then as dtgpu_batch_create_device. */
 dtgpu_status dtgpu_batch_create_decoded(dtgpu_decoded *dec, dtgpu_batch **out);
