@@ -45,10 +45,6 @@ struct Settings {
     // LDS overflow -> HBM tier hand-back with a large value)
     uint64_t lds_fill = 40;
     bool flat = true;          // the smallest LDS tier on the flat 2-level index (IX_FLAT)
-    bool plan_split = true;    // the <= 64-chain planner in two phases (walk order, then lane-parallel steps)
-    // the walk four documents per wave (walk_kernel) before the plan kernel (also for a single
-    // document: its walk then runs beside prep's second half, 12.9 -> 12.0 ms)
-    bool plan_walk = true;
     bool prep_chains = true;   // prep as three launches, the chain decomposition four documents per wave
     bool walk_overlap = true;  // the walk on its own stream beside prep's second half
     bool host_plan = false;    // walk plans built on the host

@@ -189,10 +189,8 @@ struct PlanParams {
     uint32_t lds_entries;   // per-wave LDS capacity (entries) of the todo stack / pending counts
     uint32_t max_agents;    // largest agent count among device-planned documents
     uint32_t prof;          // cycle profile into PlanResult.prof
-    uint32_t split;         // <= 64 chains: the two-phase planner (order, then lane-parallel steps)
-    uint32_t *order;        // two-phase planner: walk orders, document d's at its entry offset
-    uint32_t *walk;         // nullable: per document {status, steps} of walk_kernel (the orders
-                            // four documents per wave); null: the planner walks itself
+    uint32_t *order;        // <= 64 chains: walk_kernel's orders, document d's at its entry offset
+    uint32_t *walk;         // per document {status | stack depth << 16, steps} of walk_kernel
     const uint32_t *coff, *poff;   // walk_kernel's CSR mode: children offsets, parent offsets
     uint32_t todo_cap;             // walk_kernel: stack slots per document (0: PLAN_TODO_CAP) -- the
                                    // staging walk's deepest stack, so more walks share a CU's LDS

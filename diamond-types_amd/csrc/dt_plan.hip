@@ -16,12 +16,16 @@
 // dense per-chain seq -> LV table.  (Diamond-types' agents are not chains in general: a git
 // import has one author committing on concurrent branches.)
 //
-// vv rows (one per entry: the version vector of the entry's parents) live in HBM scratch;
-// lane l keeps chains l, l + 64, ... of the current vector (K chunks: K = 1 up to 64 chains,
-// K = 8 up to 512).  The todo stack and the pending-parent counts live in LDS.  Per consumed
-// entry the wave issues one record load (as soon as the entry is picked, overlapping the
-// previous entry's emission), one batch of independent loads (its op runs and children) and,
-// when the frontier moves sideways, one gather per 64 retreat/advance entries.
+// Three planners, one per kind of document:
+//   plan_kernel_1     <= 64 chains.  The order is walk_kernel's, always: it runs first (a 16-lane
+//                     group per document) and stores each document's spanning-tree order;
+//                     plan_doc_split walks nothing, it turns that order into commands, lane = step.
+//   plan_kernel_wide  > 64 chains (host-staged batches only).  plan_doc<K> walks and emits entry
+//                     by entry; lane l keeps chains l, l + 64, ... of the current vector
+//                     (K = PLAN_MAX_AGENTS / 64 chunks), the vv rows live in HBM scratch.
+//   plan_kernel_xf    merge requests over projected histories (xwalk / plan_doc_xf).
+// The two that walk keep the todo stack and the pending-parent counts in LDS and share the
+// seeding and the push; all three share the move to the tip, the result write and bind_doc.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -39,15 +43,15 @@ struct P {
     uint32_t ne, A, ntip, n_lv;
     // scratch: vv rows in HBM; todo stack and pending parent counts in LDS (u16)
     uint32_t *base;
-    uint32_t *order;       // two-phase planner: the walk order (ne words)
-    const uint32_t *prow;  // K = 1: each entry's parent version vector (row_stride words)
+    const uint32_t *order; // <= 64 chains: walk_kernel's order (ne words)
+    const uint32_t *prow;  // <= 64 chains: each entry's parent version vector (row_stride words)
     uint32_t row_stride;
     uint16_t *todo;      // ready entries (PLAN_TODO_CAP slots)
     uint8_t *pending;    // per entry: unvisited parents | merge flag
     // outputs
     Cmd *cmds;
     uint32_t *tlist;
-    const uint32_t *walk;  // walk_kernel's {status, steps} for this document, or null
+    const uint32_t *walk;  // <= 64 chains: walk_kernel's {status, steps} for this document
     uint32_t ccap, tcap;
     uint32_t count_only;   // sizing pass: count commands and entries, write nothing
     // wave-uniform state
@@ -192,76 +196,6 @@ DEV void emit_diff(P &p, const VV<K> &from, const VV<K> &to, const VV<K> &dlo, c
     }
 }
 
-// emit_diff for <= 64 chains split in two: emit_issue (as soon as both vectors are known)
-// computes the per-chain ranges and issues the gather of the first 64 dense-table words;
-// emit_store (after the children bookkeeping has hidden that latency) writes them and any
-// further chunks.  Same output as emit_diff<1>.
-struct Emit {
-    bool any;
-    u64 am;
-    uint32_t off, n, src, fl;    // per chain lane: output offset, count, dense source, advance flag
-    uint32_t total, n_adv;
-    uint32_t dv, dfl;            // lane u < 64: dense word and flag of output u
-};
-DEV void emit_issue(P &p, const VV<1> &from, const VV<1> &to, const VV<1> &dlo, const VV<1> &dhi,
-                    bool allow_retreat, Emit &E) {
-    const uint32_t l = lane();
-    const bool act = l < p.A && from.v[0] != to.v[0];
-    E.am = __ballot(act);
-    E.any = E.am != 0;
-    E.total = E.n_adv = 0;
-    E.dv = 0; E.dfl = 0;
-    if (!E.any) return;
-    if (__ballot(act && to.v[0] < from.v[0] && !allow_retreat)) { fail(p, PLAN_ERR_INTERNAL); E.any = false; return; }
-    const bool adv = to.v[0] > from.v[0];
-    const uint32_t s0 = adv ? from.v[0] : to.v[0];
-    const uint32_t n = act ? (adv ? to.v[0] - from.v[0] : from.v[0] - to.v[0]) : 0;
-    if (__ballot(act && dlo.v[0] + s0 + n > dhi.v[0])) { fail(p, PLAN_ERR_INTERNAL); E.any = false; return; }
-    const uint32_t inc = scan_incl(n);
-    E.total = rdl(inc, 63);
-    E.n_adv = rdl(scan_incl(adv ? n : 0), 63);
-    E.off = inc - n; E.n = n; E.src = dlo.v[0] + s0; E.fl = adv ? TL_ADV : 0u;
-    if (p.count_only) return;
-    uint32_t from_idx = 0, flag = 0;
-    for (u64 m = E.am; m; m &= m - 1) {   // the chain whose output slice holds lane l (few chains move)
-        const uint32_t j = ctz(m);
-        const uint32_t o = U(rdl(E.off, j)), nn = U(rdl(E.n, j));
-        if (o >= 64) break;
-        if (l >= o && l < o + nn) { from_idx = U(rdl(E.src, j)) + (l - o); flag = U(rdl(E.fl, j)); }
-    }
-    if (l < E.total) { E.dv = p.dense[from_idx]; E.dfl = flag; }
-}
-DEV void emit_store(P &p, const Emit &E) {
-    const uint32_t l = lane();
-    if (uint64_t(p.nt) + E.total > p.tcap) { fail(p, PLAN_TLIST_FULL); return; }
-    if (!p.count_only) {
-        bool bad = l < E.total && E.dv == 0xFFFFFFFFu;
-        if (l < E.total) p.tlist[p.nt + l] = E.dv | E.dfl;
-        // outputs past the first 64: each moving chain's slice is one contiguous copy out of its
-        // dense table
-        if (E.total > 64) {
-            for (u64 m = E.am; m; m &= m - 1) {
-                const uint32_t j = ctz(m);
-                const uint32_t o = U(rdl(E.off, j)), nn = U(rdl(E.n, j));
-                const uint32_t src = U(rdl(E.src, j)), fl = U(rdl(E.fl, j));
-                const uint32_t a = max(o, 64u), b = o + nn;
-                for (uint32_t u0 = a; u0 < b; u0 += 64) {
-                    const uint32_t u = u0 + l;
-                    if (u < b) {
-                        const uint32_t v = p.dense[src + (u - o)];
-                        if (v == 0xFFFFFFFFu) bad = true;
-                        p.tlist[p.nt + u] = v | fl;
-                    }
-                }
-            }
-        }
-        if (__ballot(bad)) { fail(p, PLAN_ERR_INTERNAL); return; }
-    }
-    p.nt += E.total;
-    p.n_adv += E.n_adv;
-    p.n_ret += E.total - E.n_adv;
-}
-
 DEV void push_cmd(P &p, uint32_t op, uint32_t a, uint32_t n, uint32_t pos) {
     if (uint64_t(p.nc) >= p.ccap) { fail(p, PLAN_CMDS_FULL); return; }
     if (lane() == 0 && !p.count_only) p.cmds[p.nc] = Cmd{op, a, n, pos};
@@ -293,6 +227,95 @@ DEV uint32_t pick(P &p, uint32_t &top) {
     return idx;
 }
 
+// Push the entries e of the `ready` lanes onto the todo stack, in lane order.
+DEV bool push_ready(P &p, uint32_t &top, bool ready, uint32_t e) {
+    const u64 m = __ballot(ready);
+    const uint32_t rank = uint32_t(__popcll(m & ((1ull << lane()) - 1ull)));
+    if (top + uint32_t(__popcll(m)) > PLAN_TODO_CAP) { fail(p, PLAN_TODO_FULL); return false; }
+    if (ready) p.todo[top + rank] = uint16_t(e);
+    top += uint32_t(__popcll(m));
+    return true;
+}
+DEV uint8_t pend_byte(uint32_t np, bool merge) { return uint8_t(min(np, 0x7Fu) | (merge ? MERGE_BIT : 0)); }
+// Seed the todo stack from the pending bytes: the roots (no parent left to wait for), highest
+// index first, so that the first root ends on top.
+DEV void seed_roots(P &p, uint32_t &top) {
+    fence_wave();
+    for (int c = int((p.ne + 63) / 64) - 1; c >= 0; c--) {
+        if (!charge(p)) break;
+        const uint32_t e = uint32_t(c) * 64 + (63 - lane());   // descending entry index across lanes
+        if (!push_ready(p, top, e < p.ne && (p.pending[e] & 0x7F) == 0, e)) break;
+    }
+    fence_wave();
+}
+// The whole-document seeding: every entry's pending byte from its parent count, then the roots.
+DEV void seed_doc(P &p, uint32_t &top) {
+    bool bad_np = false;
+    for (uint32_t e = lane(); e < p.ne; e += 64) {
+        const uint32_t np = p.erec[size_t(e) * EREC_HEAD + R_NP];
+        bad_np |= np > 0x7Fu;
+        p.pending[e] = pend_byte(np, np >= 2);
+    }
+    seed_roots(p, top);
+    if (__ballot(bad_np)) fail(p, PLAN_WIDE_MERGE);
+}
+
+// Move the tracker from one version to another: the retreat / advance entries and their TOG.
+template <int K>
+DEV void move_to(P &p, const VV<K> &from, const VV<K> &to, const VV<K> &dlo, const VV<K> &dhi, bool allow_retreat) {
+    if (!vv_differ(from, to)) return;
+    const uint32_t t0 = p.nt;
+    emit_diff<K>(p, from, to, dlo, dhi, allow_retreat);
+    if (!p.err && p.nt > t0) push_cmd(p, CMD_TOG, t0, p.nt - t0, 0);
+}
+// The last move, to the tip vt (cg.version; the replay then holds the checkout): what it advances
+// is the result's n_tip and no part of n_advance.
+template <int K>
+DEV void move_to_tip(P &p, PlanResult *res, const VV<K> &vf, const VV<K> &vt, const VV<K> &dlo, const VV<K> &dhi,
+                     bool allow_retreat) {
+    if (p.err || !vv_differ(vf, vt)) return;
+    const uint32_t adv0 = p.n_adv;
+    move_to<K>(p, vf, vt, dlo, dhi, allow_retreat);
+    res->n_tip = uint32_t(p.n_adv - adv0);
+    p.n_adv = adv0;
+}
+DEV void write_result(const P &p, PlanResult *res) {
+    if (lane() != 0) return;
+    for (int i = 0; i < 6; i++) res->prof[i] = p.prof ? g_pc[i] : 0;
+    res->status = p.err;
+    res->ncmd = p.nc; res->ntlist = p.nt;
+    res->n_retreat = p.n_ret; res->n_advance = p.n_adv;
+}
+
+// The planner's view of document pd: its slices of the batch's arrays, the wave's LDS (the todo
+// stack, then the pending bytes), empty outputs.  The callers add their scratch (base, order, walk).
+DEV void bind_doc(P &p, const PlanParams &Q, const PlanDesc &pd, uint16_t *lds16, uint64_t limit) {
+    p.erec = Q.erec + pd.erec_off;
+    p.par = Q.par + pd.par_off; p.pent = Q.pent + pd.par_off;
+    p.pch = Q.pch + pd.par_off; p.pcnt = Q.pcnt + pd.par_off;
+    p.child = Q.child + pd.child_off;
+    p.opc = Q.opc + pd.op_off;
+    p.doff = Q.doff + pd.doff_off; p.dense = Q.dense + pd.dense_off;
+    p.tip = Q.tip + pd.tip_off * 2;
+    p.ne = U(pd.ne); p.A = U(pd.n_agents); p.ntip = U(pd.ntip); p.n_lv = U(pd.n_lv);
+    p.todo = lds16;
+    p.pending = reinterpret_cast<uint8_t *>(lds16 + PLAN_TODO_CAP);
+    p.base = nullptr; p.order = nullptr; p.walk = nullptr;
+    p.prow = Q.prow + pd.prow_off; p.row_stride = pd.row_stride;
+    p.cmds = Q.cmds + pd.cmd_off; p.tlist = Q.tlist + pd.tlist_off;
+    p.count_only = Q.count_only;
+    p.ccap = Q.count_only ? 0xFFFFFFFFu : U(pd.ccap);
+    p.tcap = Q.count_only ? 0xFFFFFFFFu : U(pd.tcap);
+    p.nc = p.nt = p.err = 0;
+    p.n_ret = p.n_adv = 0;
+    p.steps = 0; p.limit = uint32_t(min<uint64_t>(limit, 0xFFFFFFF0ull));
+    p.prof = Q.prof;
+}
+
+// > 64 chains: walk and emit entry by entry.  Per consumed entry the wave issues one record load
+// (as soon as the entry is picked, overlapping the previous entry's emission), one batch of
+// independent loads (its op runs and children) and, when the frontier moves sideways, one gather
+// per 64 retreat/advance entries.
 template <int K>
 DEV void plan_doc(P &p, PlanResult *res) {
     const uint32_t l = lane();
@@ -305,29 +328,8 @@ DEV void plan_doc(P &p, PlanResult *res) {
         dlo.v[k] = a < p.A ? p.doff[a] : 0;
         dhi.v[k] = a < p.A ? p.doff[a + 1] : 0;
     }
-    // pending parent counts (+ merge flag); the todo stack holds the roots, first root on top
     uint32_t top = 0;
-    bool bad_np = false;
-    for (uint32_t c = 0; c < p.ne; c += 64) {
-        const uint32_t e = c + l;
-        if (e < p.ne) {
-            const uint32_t np = p.erec[size_t(e) * EREC_HEAD + R_NP];
-            if (np > 0x7Fu) bad_np = true;
-            p.pending[e] = uint8_t(min(np, 0x7Fu) | (np >= 2 ? MERGE_BIT : 0));
-        }
-    }
-    for (int c = int((p.ne + 63) / 64) - 1; c >= 0; c--) {
-        if (!charge(p)) break;
-        const uint32_t e = uint32_t(c) * 64 + (63 - l);   // descending entry index across lanes
-        const bool root = e < p.ne && p.erec[size_t(e) * EREC_HEAD + R_NP] == 0;
-        const u64 m = __ballot(root);
-        const uint32_t rank = uint32_t(__popcll(m & ((1ull << l) - 1ull)));
-        if (top + uint32_t(__popcll(m)) > PLAN_TODO_CAP) { fail(p, PLAN_TODO_FULL); break; }
-        if (root) p.todo[top + rank] = uint16_t(e);
-        top += uint32_t(__popcll(m));
-    }
-    if (__ballot(bad_np)) fail(p, PLAN_WIDE_MERGE);
-    fence_wave();
+    seed_doc(p, top);
     tk(p);
     PT(5);
     uint32_t f = 0xFFFFFFFFu;   // current frontier: ROOT or one LV
@@ -397,13 +399,6 @@ DEV void plan_doc(P &p, PlanResult *res) {
         vf = vp;
         fold_entry<K>(p, e_start, e_end, e_end - 1, chain, seq0, vf, true);
         if (p.err) break;
-        // K = 1: the retreat / advance gather is issued now and stored after the children work
-        Emit em;
-        em.any = false;
-        if constexpr (K == 1) {
-            if (vv_differ(v_old, vp)) emit_issue(p, v_old, vp, dlo, dhi, true, em);
-            if (p.err) break;
-        }
         // children whose last parent this was become ready (pushed in child index order); the
         // next entry is picked and its record requested before this entry's output is written
         for (uint32_t c = 0; c < nch; c += 64) {
@@ -414,11 +409,7 @@ DEV void plan_doc(P &p, PlanResult *res) {
                 p.pending[chv] = pd;
                 ready = (pd & 0x7F) == 0;
             }
-            const u64 m = __ballot(ready);
-            const uint32_t rank = uint32_t(__popcll(m & ((1ull << l) - 1ull)));
-            if (top + uint32_t(__popcll(m)) > PLAN_TODO_CAP) { fail(p, PLAN_TODO_FULL); break; }
-            if (ready) p.todo[top + rank] = uint16_t(chv);
-            top += uint32_t(__popcll(m));
+            if (!push_ready(p, top, ready, chv)) break;
         }
         fence_wave();
         have = top > 0;
@@ -428,19 +419,8 @@ DEV void plan_doc(P &p, PlanResult *res) {
         }
         PT(2);
         // retreat / advance to the parents, then apply the entry's op runs
-        if constexpr (K == 1) {
-            if (em.any) {
-                const uint32_t t0 = p.nt;
-                emit_store(p, em);
-                if (p.err) break;
-                if (p.nt > t0) push_cmd(p, CMD_TOG, t0, p.nt - t0, 0);
-            }
-        } else if (vv_differ(v_old, vp)) {
-            const uint32_t t0 = p.nt;
-            emit_diff<K>(p, v_old, vp, dlo, dhi, true);
-            if (p.err) break;
-            if (p.nt > t0) push_cmd(p, CMD_TOG, t0, p.nt - t0, 0);
-        }
+        move_to<K>(p, v_old, vp, dlo, dhi, true);
+        if (p.err) break;
         PT(3);
         if (uint64_t(p.nc) + nop > p.ccap) { fail(p, PLAN_CMDS_FULL); break; }
         if (!p.count_only) {
@@ -454,7 +434,6 @@ DEV void plan_doc(P &p, PlanResult *res) {
         f = e_end - 1;
         PT(4);
     }
-    // advance to the tip (cg.version): the replay then holds the checkout
     if (!p.err) {
         VV<K> vt;
         vv_zero(vt);
@@ -463,277 +442,9 @@ DEV void plan_doc(P &p, PlanResult *res) {
             vv_at<K>(p, U(p.tip[2 * j]), U(p.tip[2 * j + 1]), t);
             vv_max(vt, t);
         }
-        if (!p.err && vv_differ(vf, vt)) {
-            const uint32_t t0 = p.nt;
-            const uint32_t adv0 = p.n_adv;
-            emit_diff<K>(p, vf, vt, dlo, dhi, false);
-            if (!p.err && p.nt > t0) push_cmd(p, CMD_TOG, t0, p.nt - t0, 0);
-            res->n_tip = uint32_t(p.n_adv - adv0);
-            p.n_adv = adv0;
-        }
+        move_to_tip<K>(p, res, vf, vt, dlo, dhi, false);
     }
-    if (l == 0) {
-        for (int i = 0; i < 6; i++) res->prof[i] = p.prof ? g_pc[i] : 0;
-        res->status = p.err;
-        res->ncmd = p.nc;
-        res->ntlist = p.nt;
-        res->n_retreat = p.n_ret;
-        res->n_advance = p.n_adv;
-    }
-}
-
-// ---- <= 64 chains: the software-pipelined walk ------------------------------------------------
-//
-// Same walk, same output as plan_doc<1>, reordered so that one entry's memory round trips hide
-// behind another's work:
-//   * the ready stack lives in registers (Stk below): a push or pick is a few lane operations,
-//     not a chain of dependent LDS reads;
-//   * the next entry is picked right after the current entry's children are counted (a child
-//     list of <= 2 comes from the record: its first and last child), and its record and its
-//     parent version vector are requested before this entry's diff work;
-//   * the parent version vector of every entry is precomputed (the prep kernel's chain
-//     decomposition / build_plan_input compute it anyway), so a merge costs no parent-row
-//     round trips;
-//   * this entry's retreat / advance gather is issued, and written out (with its op-run
-//     commands) one iteration later, behind the next entry's children / pick.
-// The record sits in one VGPR (lane k: word k), fields broadcast on demand.  (Through the
-// scalar cache it would share lgkmcnt with the walk's LDS traffic: every LDS read after the
-// s_load would wait for it -- measured slower.)
-struct Rec { uint32_t w, row; };   // the record and the entry's parent version vector (lane = chain)
-DEV Rec srec(const P &p, uint32_t e) {
-    const uint32_t l = lane();
-    return Rec{load_rec(p, e), l < p.A ? p.prow[size_t(e) * p.row_stride + l] : 0u};
-}
-DEV uint32_t F(const Rec &r, int k) { return R(r.w, k); }
-
-// The ready stack with its top 64 entries in registers: lane i holds position nl + i (the
-// nl bottom entries sit in LDS todo[0, nl)), bit i of mm says whether lane i's entry is a merge.
-// Pushes, pops and the merge-skipping pick (txn_trace.rs:249-266, same positions as pick()) are
-// register operations; LDS is touched only when the stack outgrows 64 or drains into its
-// bottom part.
-struct Stk {
-    uint32_t v;      // lane i: entry at position nl + i (i < n)
-    u64 mm;          // merge flags of the register part
-    uint32_t n, nl;  // entries in registers / in LDS
-};
-// Push the lanes of `ready` (child index order = lane order), entry in chv, merge flag in mg.
-DEV bool stk_push(P &p, Stk &S, u64 ready, uint32_t chv, bool mg) {
-    const uint32_t l = lane();
-    const uint32_t cnt = uint32_t(__popcll(ready));
-    if (!cnt) return true;
-    if (S.nl + S.n + cnt > PLAN_TODO_CAP) { fail(p, PLAN_TODO_FULL); return false; }
-    if (S.n + cnt > 64) {   // spill the register part to LDS (merge flags stay in pending[])
-        if (l < S.n) p.todo[S.nl + l] = uint16_t(S.v);
-        S.nl += S.n;
-        S.n = 0;
-        S.mm = 0;
-        fence_wave();
-    }
-    // ready lanes in lane order onto positions n, n + 1, ... (usually one or two)
-    const u64 mgm = __ballot(mg);
-    uint32_t at = S.n;
-    for (u64 r = ready; r; r &= r - 1, at++) {
-        const uint32_t j = ctz(r);
-        const uint32_t e = rdl(chv, j);
-        S.v = l == at ? e : S.v;
-        if ((mgm >> j) & 1ull) S.mm |= 1ull << at;
-    }
-    S.n += cnt;
-    return true;
-}
-// Pop the next entry (as pick()); has_any: S.n + S.nl > 0.
-DEV uint32_t stk_pick(P &p, Stk &S) {
-    const uint32_t l = lane();
-    if (S.n == 0) {   // refill from LDS: its top 32 (or fewer) positions
-        const uint32_t k = min(S.nl, 32u);
-        const uint32_t base = S.nl - k;
-        const uint32_t e = l < k ? uint32_t(p.todo[base + l]) : 0u;
-        const bool mg = l < k && (p.pending[e] & MERGE_BIT);
-        S.v = e;
-        S.mm = __ballot(mg);
-        S.n = k;
-        S.nl = base;
-    }
-    const uint32_t t = S.n - 1;
-    uint32_t idx = rdl(S.v, t);
-    if ((S.mm >> t) & 1ull) {
-        const u64 nm = ~S.mm & ((1ull << t) - 1ull);
-        if (nm) {   // the highest non-merge below the top takes its place
-            const uint32_t pos = 63u - uint32_t(__clzll((long long)nm));
-            const uint32_t x = rdl(S.v, pos);
-            S.v = l == pos ? idx : S.v;
-            S.mm |= 1ull << pos;
-            idx = x;
-        } else if (S.nl) {   // scan the LDS part, top down
-            int found = -1;
-            for (int hi = int(S.nl) - 1; hi >= 0 && found < 0; hi -= 64) {
-                const int i = hi - int(l);
-                const bool ok = i >= 0 && !(p.pending[p.todo[i]] & MERGE_BIT);
-                const u64 m = __ballot(ok);
-                if (m) found = hi - int(ctz(m));
-            }
-            if (found >= 0) {
-                const uint32_t x = U(p.todo[found]);
-                if (l == 0) p.todo[found] = uint16_t(idx);
-                fence_wave();
-                idx = x;
-            }
-        }
-    }
-    S.mm &= ~(1ull << t);
-    S.n--;
-    return U(idx);
-}
-
-DEV void plan_doc1(P &p, PlanResult *res) {
-    const uint32_t l = lane();
-    const uint32_t dlo = l < p.A ? p.doff[l] : 0, dhi = l < p.A ? p.doff[l + 1] : 0;
-    VV<1> dl, dh;
-    dl.v[0] = dlo; dh.v[0] = dhi;
-    uint32_t top = 0;
-    bool bad_np = false;
-    for (uint32_t c = 0; c < p.ne; c += 64) {
-        const uint32_t e = c + l;
-        if (e < p.ne) {
-            const uint32_t np = p.erec[size_t(e) * EREC_HEAD + R_NP];
-            if (np > 0x7Fu) bad_np = true;
-            p.pending[e] = uint8_t(min(np, 0x7Fu) | (np >= 2 ? MERGE_BIT : 0));
-        }
-    }
-    for (int c = int((p.ne + 63) / 64) - 1; c >= 0; c--) {
-        if (!charge(p)) break;
-        const uint32_t e = uint32_t(c) * 64 + (63 - l);
-        const bool root = e < p.ne && p.erec[size_t(e) * EREC_HEAD + R_NP] == 0;
-        const u64 m = __ballot(root);
-        const uint32_t rank = uint32_t(__popcll(m & ((1ull << l) - 1ull)));
-        if (top + uint32_t(__popcll(m)) > PLAN_TODO_CAP) { fail(p, PLAN_TODO_FULL); break; }
-        if (root) p.todo[top + rank] = uint16_t(e);
-        top += uint32_t(__popcll(m));
-    }
-    if (__ballot(bad_np)) fail(p, PLAN_WIDE_MERGE);
-    fence_wave();
-    Stk S;
-    S.v = 0; S.mm = 0; S.n = 0; S.nl = top;
-    tk(p);
-    PT(5);
-    VV<1> vf;
-    vf.v[0] = 0;
-    // the previous entry's deferred output: its diff (gather in flight) and its op runs
-    Emit pe_em;
-    pe_em.any = false;
-    uint32_t pe_nop = 0, pe_op0 = 0;
-    uint4 pe_oc = make_uint4(0, 0, 0, 0);
-    bool pe_have = false;
-    const uint4 *opw4 = reinterpret_cast<const uint4 *>(p.opc);
-    auto flush = [&]() {   // the previous entry's TOG, tlist slice and op-run commands
-        if (!pe_have) return;
-        if (pe_em.any) {
-            const uint32_t t0 = p.nt;
-            emit_store(p, pe_em);
-            if (p.err) return;
-            if (p.nt > t0) push_cmd(p, CMD_TOG, t0, p.nt - t0, 0);
-        }
-        if (uint64_t(p.nc) + pe_nop > p.ccap) { fail(p, PLAN_CMDS_FULL); return; }
-        if (!p.count_only) {
-            uint4 *cw = reinterpret_cast<uint4 *>(p.cmds) + p.nc;
-            if (l < pe_nop) cw[l] = pe_oc;
-            for (uint32_t j = 64 + l; j < pe_nop; j += 64) cw[j] = opw4[pe_op0 + j];
-        }
-        p.nc += pe_nop;
-        pe_have = false;
-    };
-    bool have = S.nl > 0;
-    uint32_t idx = have ? stk_pick(p, S) : 0;
-    Rec rc;
-    if (have) rc = srec(p, idx);
-    while (have && !p.err) {
-        if (!charge(p)) break;
-        const uint32_t nch = F(rc, R_NCH), ch0 = F(rc, R_CH0), lastch = F(rc, R_LASTCH), firstch = F(rc, R_FIRSTCH);
-        PT(0);
-        // children whose last parent this is become ready (pushed in child index order); the
-        // next entry is picked and its record requested before this entry's own work
-        uint32_t ch = l == 0 ? firstch : lastch;
-        if (nch > 2) ch = l < nch ? p.child[ch0 + l] : 0;
-        for (uint32_t c = 0; c < nch; c += 64) {
-            const uint32_t chv = c == 0 ? ch : (c + l < nch ? p.child[ch0 + c + l] : 0);
-            bool ready = false, mg = false;
-            if (c + l < nch) {
-                const uint8_t pd = uint8_t(p.pending[chv] - 1);
-                p.pending[chv] = pd;
-                ready = (pd & 0x7F) == 0;
-                mg = (pd & MERGE_BIT) != 0;
-            }
-            if (!stk_push(p, S, __ballot(ready), chv, mg)) break;
-        }
-        if (p.err) break;
-        have = S.n + S.nl > 0;
-        uint32_t nidx = 0;
-        Rec nrc;
-        if (have) {
-            nidx = stk_pick(p, S);
-            nrc = srec(p, nidx);
-        }
-        PT(2);
-        // this entry's op runs (written out with its diff one iteration later)
-        const uint32_t op0 = F(rc, R_OP0), nop = F(rc, R_NOP);
-        uint4 oc = make_uint4(0, 0, 0, 0);
-        if (l < nop && !p.count_only) oc = opw4[op0 + l];
-        // the previous entry's output (its gather has been in flight since the end of its
-        // iteration)
-        flush();
-        if (p.err) break;
-        PT(4);
-        const uint32_t e_start = F(rc, R_START), e_end = F(rc, R_END), po = F(rc, R_POFF), np = F(rc, R_NP);
-        const uint32_t chain = F(rc, R_CHAIN), seq0 = F(rc, R_SEQ0), par0 = F(rc, R_PAR0);
-        // version vector of the parents: the entry's precomputed row
-        VV<1> vp;
-        vp.v[0] = rc.row;
-        (void)po; (void)np; (void)par0;
-        PT(1);
-        const VV<1> v_old = vf;
-        vf = vp;
-        fold_entry<1>(p, e_start, e_end, e_end - 1, chain, seq0, vf, true);
-        if (p.err) break;
-        pe_em.any = false;
-        if (vv_differ(v_old, vp)) emit_issue(p, v_old, vp, dl, dh, true, pe_em);
-        if (p.err) break;
-        pe_have = true;
-        pe_nop = nop; pe_op0 = op0;
-        pe_oc = oc;
-        idx = nidx;
-        rc = nrc;
-        PT(3);
-    }
-    if (!p.err) flush();
-    // advance to the tip (cg.version): the replay then holds the checkout
-    if (!p.err) {
-        VV<1> vt;
-        vv_zero(vt);
-        for (uint32_t j = 0; j < p.ntip; j++) {
-            const uint32_t tlv = U(p.tip[2 * j]), te = U(p.tip[2 * j + 1]);
-            const Rec tr = srec(p, te);
-            VV<1> t;
-            t.v[0] = tr.row;
-            fold_entry<1>(p, F(tr, R_START), F(tr, R_END), tlv, F(tr, R_CHAIN), F(tr, R_SEQ0), t, false);
-            vv_max(vt, t);
-        }
-        if (!p.err && vv_differ(vf, vt)) {
-            const uint32_t t0 = p.nt;
-            const uint32_t adv0 = p.n_adv;
-            emit_diff<1>(p, vf, vt, dl, dh, false);
-            if (!p.err && p.nt > t0) push_cmd(p, CMD_TOG, t0, p.nt - t0, 0);
-            res->n_tip = uint32_t(p.n_adv - adv0);
-            p.n_adv = adv0;
-        }
-    }
-    if (l == 0) {
-        for (int i = 0; i < 6; i++) res->prof[i] = p.prof ? g_pc[i] : 0;
-        res->status = p.err;
-        res->ncmd = p.nc;
-        res->ntlist = p.nt;
-        res->n_retreat = p.n_ret;
-        res->n_advance = p.n_adv;
-    }
+    write_result(p, res);
 }
 
 // ---- <= 64 chains, two phases -----------------------------------------------------------------
@@ -742,99 +453,44 @@ DEV void plan_doc1(P &p, PlanResult *res) {
 // depends only on the step's entry and the one before it: the frontier before step i is the
 // previous entry's parent vector with that entry's own LVs folded in (fold_entry), the frontier it
 // moves to is entry i's parent vector.  So:
-//   phase A (sequential, wave-uniform): the spanning-tree order alone -- pick, children
-//     bookkeeping, one record load per step -- written to the document's scratch (p.base);
-//   phase B (lane-parallel, lane = walk step): each step's retreat / advance ranges and op runs
-//     sized, offsets by prefix sums, then every step's TOG command, tlist slice and op-run
+//   phase A (walk_kernel, launched before this kernel): the spanning-tree order alone -- pick,
+//     children bookkeeping, one record load per step -- stored in p.order, its status and step
+//     count in p.walk;
+//   phase B (here; lane-parallel, lane = walk step): each step's retreat / advance ranges and op
+//     runs sized, offsets by prefix sums, then every step's TOG command, tlist slice and op-run
 //     commands written by its own lane.
-// Same output as plan_doc1 (tested against the host walk).
+// The order is walk_kernel's and nobody else's: this function walks nothing.  Its output is the
+// sequential walk's (plan_doc's, and the host planner's, which the tests compare it with).
 constexpr uint32_t kSplitLaneTl = 24, kSplitLaneOps = 8;   // per-lane step writes up to these sizes
 constexpr uint32_t kSplitRegChains = 4;   // up to this many moving chains per step: output-parallel chunk writes
-constexpr uint32_t kSplitSegChunk = 4096;
-constexpr uint32_t kSplitCopyDepth = 8;   // big steps: 8 x 64 dense-table loads per round trip   // ... for chunks writing up to this many entries / commands
+constexpr uint32_t kSplitSegChunk = 4096; // ... for chunks writing up to this many entries / commands
+constexpr uint32_t kSplitCopyDepth = 8;   // big steps: 8 x 64 dense-table loads per round trip
+
+// The record and the entry's parent version vector (lane = chain), lane by lane.
+struct Rec { uint32_t w, row; };
+DEV Rec srec(const P &p, uint32_t e) {
+    const uint32_t l = lane();
+    return Rec{load_rec(p, e), l < p.A ? p.prow[size_t(e) * p.row_stride + l] : 0u};
+}
+DEV uint32_t F(const Rec &r, int k) { return R(r.w, k); }
+
 DEV void plan_doc_split(P &p, PlanResult *res) {
     const uint32_t l = lane();
-    uint32_t top = 0;
-    bool bad_np = false;
-    for (uint32_t c = 0; c < p.ne && !p.walk; c += 64) {
-        const uint32_t e = c + l;
-        if (e < p.ne) {
-            const uint32_t np = p.erec[size_t(e) * EREC_HEAD + R_NP];
-            if (np > 0x7Fu) bad_np = true;
-            p.pending[e] = uint8_t(min(np, 0x7Fu) | (np >= 2 ? MERGE_BIT : 0));
-        }
-    }
-    for (int c = p.walk ? -1 : int((p.ne + 63) / 64) - 1; c >= 0; c--) {
-        if (!charge(p)) break;
-        const uint32_t e = uint32_t(c) * 64 + (63 - l);
-        const bool root = e < p.ne && p.erec[size_t(e) * EREC_HEAD + R_NP] == 0;
-        const u64 m = __ballot(root);
-        const uint32_t rank = uint32_t(__popcll(m & ((1ull << l) - 1ull)));
-        if (top + uint32_t(__popcll(m)) > PLAN_TODO_CAP) { fail(p, PLAN_TODO_FULL); break; }
-        if (root) p.todo[top + rank] = uint16_t(e);
-        top += uint32_t(__popcll(m));
-    }
-    if (__ballot(bad_np)) fail(p, PLAN_WIDE_MERGE);
-    fence_wave();
     tk(p);
     PT(5);
-    // ---- phase A: the order (walk_kernel's, when it ran) ----
-    uint32_t *order = p.order;   // ne words
-    Stk S;
-    S.v = 0; S.mm = 0; S.n = 0; S.nl = top;
-    bool have = S.nl > 0 && !p.err && !p.walk;
-    uint32_t idx = have ? stk_pick(p, S) : 0;
-    uint32_t rw = have ? load_rec(p, idx) : 0;
-    uint32_t ns = 0;
-    uint32_t ordv = 0;   // lane j: order[64 * (ns / 64) + j] until its 64 are stored together
-    if (p.walk) {
-        const uint32_t wst = U(p.walk[0]) & 0xFFFFu;   // (high 16 bits: the walk's stack depth)
-        ns = U(p.walk[1]);
-        if (wst) fail(p, wst);
-    }
-    while (have && !p.err) {
-        if (!charge(p)) break;
-        if (ns >= p.ne) { fail(p, PLAN_ERR_INTERNAL); break; }
-        ordv = l == (ns & 63u) ? idx : ordv;
-        if ((ns & 63u) == 63u) order[ns - 63 + l] = ordv;
-        ns++;
-        const uint32_t nch = R(rw, R_NCH), ch0 = R(rw, R_CH0), lastch = R(rw, R_LASTCH), firstch = R(rw, R_FIRSTCH);
-        uint32_t ch = l == 0 ? firstch : lastch;
-        if (nch > 2) ch = l < nch ? p.child[ch0 + l] : 0;
-        for (uint32_t c = 0; c < nch; c += 64) {
-            const uint32_t chv = c == 0 ? ch : (c + l < nch ? p.child[ch0 + c + l] : 0);
-            bool ready = false, mg = false;
-            if (c + l < nch) {
-                const uint8_t pd = uint8_t(p.pending[chv] - 1);
-                p.pending[chv] = pd;
-                ready = (pd & 0x7F) == 0;
-                mg = (pd & MERGE_BIT) != 0;
-            }
-            if (!stk_push(p, S, __ballot(ready), chv, mg)) break;
-        }
-        if (p.err) break;
-        have = S.n + S.nl > 0;
-        if (have) {
-            idx = stk_pick(p, S);
-            rw = load_rec(p, idx);
-        }
-    }
-    if (!p.walk && (ns & 63u) && l < (ns & 63u)) order[(ns & ~63u) + l] = ordv;
+    // ---- phase A: walk_kernel's order, its status and its step count ----
+    const uint32_t *order = p.order;   // ne words
+    const uint32_t ns = U(p.walk[1]);
+    if (const uint32_t wst = U(p.walk[0]) & 0xFFFFu) fail(p, wst);   // (high 16 bits: the walk's stack depth)
     PT(0);
-    // every lane reads the order phase A wrote
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    // each chain's dense-table slice, in LDS (the todo stack's space: phase A is done): A + 1
+    // each chain's dense-table slice, in LDS (the todo stack's space: nothing walks here): A + 1
     // offsets, one more than the lanes at 64 chains
     uint32_t *sdoff = reinterpret_cast<uint32_t *>(p.todo);
     for (uint32_t a = l; a <= p.A; a += 64) sdoff[a] = p.doff[a];
     fence_wave();
     // ---- phase B: per step, lane = step ----
-    const uint32_t A = p.A;
-    const uint32_t rs = p.row_stride;
-    uint32_t err_step = 0xFFFFFFFFu, err_code = 0;
-    uint32_t last_e = 0;
+    const uint32_t A = p.A, rs = p.row_stride;
+    uint32_t err_code = 0, last_e = 0;
     for (uint32_t c0 = 0; c0 < ns && !p.err; c0 += 64) {
         const uint32_t i = c0 + l;
         const bool valid = i < ns;
@@ -896,9 +552,8 @@ DEV void plan_doc_split(P &p, PlanResult *res) {
         const uint32_t sum_c = rdl(ic, 63), sum_t = rdl(it, 63);
         const uint32_t sum_adv = rdl(scan_incl(nadv), 63);
         PT(1);
-        if (code) { err_step = i; err_code = code; }
         const u64 em = __ballot(code != 0);
-        if (em) {   // the first failing step ends the walk, as plan_doc1 stops there
+        if (em) {   // the first failing step ends the walk, as a sequential walk stops there
             fail(p, rdl(code, ctz(em)));
             break;
         }
@@ -974,7 +629,7 @@ DEV void plan_doc_split(P &p, PlanResult *res) {
                     if (u < sum_c) p.cmds[C0 + u] = cv[q];
                 }
             }
-            if (bad) { err_step = i; err_code = PLAN_ERR_INTERNAL; }
+            if (bad) err_code = PLAN_ERR_INTERNAL;
         }
         if (!p.count_only && valid && !big && !outpar) {
             uint32_t cw = co;
@@ -1007,7 +662,7 @@ DEV void plan_doc_split(P &p, PlanResult *res) {
                 }
             }
             for (uint32_t j = 0; j < nop; j++) p.cmds[cw + j] = p.opc[op0 + j];
-            if (bad) { err_step = i; err_code = PLAN_ERR_INTERNAL; }
+            if (bad) err_code = PLAN_ERR_INTERNAL;
         }
         PT(2);
         if (!p.count_only) {
@@ -1063,9 +718,8 @@ DEV void plan_doc_split(P &p, PlanResult *res) {
         p.n_ret += sum_t - sum_adv;
         last_e = U(rdl(e, min(63u, ns - 1 - c0)));
     }
-    (void)err_step;
     PT(3);
-    // advance to the tip (cg.version): from the last step's entry folded
+    // the move to the tip starts from the last step's entry folded
     if (!p.err) {
         VV<1> vf;
         vf.v[0] = 0;
@@ -1087,28 +741,14 @@ DEV void plan_doc_split(P &p, PlanResult *res) {
             fold_entry<1>(p, F(tr, R_START), F(tr, R_END), tlv, F(tr, R_CHAIN), F(tr, R_SEQ0), t, false);
             vv_max(vt, t);
         }
-        if (!p.err && vv_differ(vf, vt)) {
-            const uint32_t t0 = p.nt;
-            const uint32_t adv0 = p.n_adv;
-            emit_diff<1>(p, vf, vt, dl, dh, false);
-            if (!p.err && p.nt > t0) push_cmd(p, CMD_TOG, t0, p.nt - t0, 0);
-            res->n_tip = uint32_t(p.n_adv - adv0);
-            p.n_adv = adv0;
-        }
+        move_to_tip<1>(p, res, vf, vt, dl, dh, false);
     }
-    if (l == 0) {
-        for (int i = 0; i < 6; i++) res->prof[i] = p.prof ? g_pc[i] : 0;
-        res->status = p.err;
-        res->ncmd = p.nc;
-        res->ntlist = p.nt;
-        res->n_retreat = p.n_ret;
-        res->n_advance = p.n_adv;
-    }
+    write_result(p, res);
 }
 
 // K = agent chunks per lane.  Documents with <= 64 agents run in the K = 1 instantiation, the
 // others (<= PLAN_MAX_AGENTS) in the wide one; each kernel skips the other's documents.
-template <int K, bool SPLIT = false>
+template <int K>
 DEV void plan_entry(const PlanParams &Q) {
     extern __shared__ __attribute__((aligned(16))) uint16_t lds16[];
     if (blockIdx.x >= Q.n_docs) return;
@@ -1116,63 +756,26 @@ DEV void plan_entry(const PlanParams &Q) {
     const PlanDesc pd = Q.docs[d];
     PlanResult *res = Q.results + d;
     if (pd.skip) return;   // planned on the host
-    const uint32_t A = U(pd.n_agents);
-    if (K == 1 ? A > 64 : A <= 64) return;
+    if (K == 1 ? pd.n_agents > 64 : pd.n_agents <= 64) return;
     P p;
-    p.erec = Q.erec + pd.erec_off;
-    p.par = Q.par + pd.par_off;
-    p.pent = Q.pent + pd.par_off;
-    p.pch = Q.pch + pd.par_off;
-    p.pcnt = Q.pcnt + pd.par_off;
-    p.child = Q.child + pd.child_off;
-    p.opc = Q.opc + pd.op_off;
-    p.doff = Q.doff + pd.doff_off;
-    p.dense = Q.dense + pd.dense_off;
-    p.tip = Q.tip + pd.tip_off * 2;
-    p.ne = U(pd.ne);
-    p.A = A;
-    p.ntip = U(pd.ntip);
-    p.n_lv = U(pd.n_lv);
-    p.todo = lds16;
-    p.pending = reinterpret_cast<uint8_t *>(lds16 + PLAN_TODO_CAP);
+    bind_doc(p, Q, pd, lds16, 1024ull * (uint64_t(pd.ne) + 16) + 4ull * pd.n_lv + (1u << 20));
     p.base = Q.base + pd.base_off;
-    p.prow = Q.prow + pd.prow_off;
     p.order = Q.order + pd.erec_off / EREC_WORDS;
-    p.walk = SPLIT && Q.walk ? Q.walk + 2 * size_t(d) : nullptr;
-    p.row_stride = pd.row_stride;
-    p.cmds = Q.cmds + pd.cmd_off;
-    p.tlist = Q.tlist + pd.tlist_off;
-    p.count_only = Q.count_only;
-    p.ccap = Q.count_only ? 0xFFFFFFFFu : U(pd.ccap);
-    p.tcap = Q.count_only ? 0xFFFFFFFFu : U(pd.tcap);
-    p.nc = p.nt = p.err = 0;
-    p.steps = 0;
-    p.limit = uint32_t(min<uint64_t>(1024ull * (uint64_t(p.ne) + 16) + 4ull * pd.n_lv + (1u << 20), 0xFFFFFFF0ull));
-    p.n_ret = p.n_adv = 0;
-    p.prof = Q.prof;
+    p.walk = Q.walk + 2 * size_t(d);
     res->n_tip = 0;
     if (p.ne > Q.lds_entries) {
         if (lane() == 0) res->status = PLAN_ERR_INTERNAL;
         return;
     }
-#ifndef DTGPU_PLAN_OLD
-    if constexpr (K == 1) {
-        if constexpr (SPLIT) plan_doc_split(p, res);
-        else plan_doc1(p, res);
-    } else {
-        plan_doc<K>(p, res);
-    }
-#else
-    plan_doc<K>(p, res);
-#endif
+    if constexpr (K == 1) plan_doc_split(p, res);
+    else plan_doc<K>(p, res);
 }
 
 #ifndef DTGPU_PLAN_WAVES
 #define DTGPU_PLAN_WAVES 6   // occupancy target of the <= 64-chain planner (tuning knob)
 #endif
-template <bool SPLIT>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DTGPU_PLAN_WAVES))) void plan_kernel_1(PlanParams Q) {
-    plan_entry<1, SPLIT>(Q);
+    plan_entry<1>(Q);
 }
 __global__ __launch_bounds__(64) void plan_kernel_wide(PlanParams Q) { plan_entry<PLAN_MAX_AGENTS / 64>(Q); }
 
@@ -1364,12 +967,6 @@ DEV void xvv_at(P &p, uint32_t lv, VV<1> &row, uint32_t &c, uint32_t &n) {
     n = R(rw, R_SEQ0) + (lv - R(rw, R_START)) + 1;
     fold_entry<1>(p, R(rw, R_START), R(rw, R_END), lv, c, R(rw, R_SEQ0), row, false);
 }
-DEV void xmove(P &p, const VV<1> &from, const VV<1> &to, const VV<1> &dlo, const VV<1> &dhi) {
-    if (!vv_differ(from, to)) return;
-    const uint32_t t0 = p.nt;
-    emit_diff<1>(p, from, to, dlo, dhi, true);
-    if (!p.err && p.nt > t0) push_cmd(p, CMD_TOG, t0, p.nt - t0, 0);
-}
 // The entry's op runs clipped to the LVs [s, t) (truncate_tagged_span; XfPlanner::apply).
 DEV void xapply(P &p, XS &x, uint32_t op0, uint32_t nop, uint32_t s, uint32_t t) {
     const uint32_t l = lane();
@@ -1427,20 +1024,9 @@ DEV void xwalk(P &p, XS &x, uint32_t bound, VV<1> &vf, const VV<1> &vF, const VV
         }
         // (an entry outside this walk: 0x7F without the merge bit, which no entry of the walk holds --
         // a non-merge has at most one parent -- and which never reaches zero: it is never decremented)
-        if (valid) p.pending[e] = in ? uint8_t(min(pend, 0x7Fu) | (mg ? MERGE_BIT : 0)) : uint8_t(0x7F);
+        if (valid) p.pending[e] = in ? pend_byte(pend, mg) : uint8_t(0x7F);
     }
-    fence_wave();
-    for (int c = int((p.ne + 63) / 64) - 1; c >= 0; c--) {   // the roots, the first one on top
-        if (!charge(p)) break;
-        const uint32_t e = uint32_t(c) * 64 + (63 - l);
-        const bool root = e < p.ne && (p.pending[e] & 0x7F) == 0;
-        const u64 m = __ballot(root);
-        const uint32_t rank = uint32_t(__popcll(m & ((1ull << l) - 1ull)));
-        if (top + uint32_t(__popcll(m)) > PLAN_TODO_CAP) { fail(p, PLAN_TODO_FULL); break; }
-        if (root) p.todo[top + rank] = uint16_t(e);
-        top += uint32_t(__popcll(m));
-    }
-    fence_wave();
+    seed_roots(p, top);
     while (top > 0 && !p.err) {
         if (!charge(p)) break;
         const uint32_t idx = pick(p, top);
@@ -1455,7 +1041,7 @@ DEV void xwalk(P &p, XS &x, uint32_t bound, VV<1> &vf, const VV<1> &vF, const VV
         VV<1> vp;
         xrow(p, idx, vp);
         if (l == chain) vp.v[0] = max(vp.v[0], seq0 + (s - st));
-        xmove(p, vf, vp, dlo, dhi);
+        move_to<1>(p, vf, vp, dlo, dhi, true);
         if (p.err) break;
         xapply(p, x, op0, nop, s, t);
         if (p.err) break;
@@ -1486,11 +1072,7 @@ DEV void xwalk(P &p, XS &x, uint32_t bound, VV<1> &vf, const VV<1> &vF, const VV
                     ready = (pd & 0x7F) == 0;
                 }
             }
-            const u64 m = __ballot(ready);
-            const uint32_t rank = uint32_t(__popcll(m & ((1ull << l) - 1ull)));
-            if (top + uint32_t(__popcll(m)) > PLAN_TODO_CAP) { fail(p, PLAN_TODO_FULL); break; }
-            if (ready) p.todo[top + rank] = uint16_t(chv);
-            top += uint32_t(__popcll(m));
+            if (!push_ready(p, top, ready, chv)) break;
         }
         fence_wave();
     }
@@ -1503,11 +1085,9 @@ DEV void plan_doc_xf(P &p, XS &x, const uint32_t *from, uint32_t n_from, PlanRes
     vv_zero(vF);
     dlo.v[0] = l < p.A ? p.doff[l] : 0;
     dhi.v[0] = l < p.A ? p.doff[l + 1] : 0;
-    {   // a parent count past the pending byte: as the whole-document planner
-        bool bad_np = false;
-        for (uint32_t e = l; e < p.ne; e += 64) bad_np |= p.erec[size_t(e) * EREC_HEAD + R_NP] > 0x7Fu;
-        if (__ballot(bad_np)) fail(p, PLAN_WIDE_MERGE);
-    }
+    bool bad_np = false;   // a parent count past the pending byte: as the whole-document planner
+    for (uint32_t e = l; e < p.ne; e += 64) bad_np |= p.erec[size_t(e) * EREC_HEAD + R_NP] > 0x7Fu;
+    if (__ballot(bad_np)) fail(p, PLAN_WIDE_MERGE);
     // vF, and `from` reduced to a frontier (lane j: its j-th LV, ascending as given): an LV is
     // dominated when another one's history reaches it on its chain.  Serial over the set, quadratic
     // for the LVs that end their chain's part of it: the caller bounds the set (MERGE_MAX_FROM)
@@ -1547,7 +1127,7 @@ DEV void plan_doc_xf(P &p, XS &x, const uint32_t *from, uint32_t n_from, PlanRes
     // phase A: Hist(from), then the tracker at `from`
     x.rep = 0;
     if (!p.err && n_from) xwalk<false>(p, x, 0, vf, vF, dlo, dhi);
-    if (!p.err) xmove(p, vf, vF, dlo, dhi);
+    if (!p.err) move_to<1>(p, vf, vF, dlo, dhi, true);
     vf = vF;
     const uint32_t first = p.nc;
     x.rep = 1;
@@ -1605,23 +1185,10 @@ DEV void plan_doc_xf(P &p, XS &x, const uint32_t *from, uint32_t n_from, PlanRes
             xvv_at(p, lv, t, c, n);
             vv_max(vt, t);
         }
-        if (!p.err && vv_differ(vf, vt)) {
-            const uint32_t adv0 = p.n_adv;
-            xmove(p, vf, vt, dlo, dhi);
-            res->n_tip = uint32_t(p.n_adv - adv0);
-            p.n_adv = adv0;
-        }
+        move_to_tip<1>(p, res, vf, vt, dlo, dhi, true);
     }
-    if (l == 0) {
-        for (int i = 0; i < 6; i++) res->prof[i] = p.prof ? g_pc[i] : 0;
-        res->status = p.err;
-        res->ncmd = p.nc;
-        res->ntlist = p.nt;
-        res->n_retreat = p.n_ret;
-        res->n_advance = p.n_adv;
-        res->xf_first = first;
-        res->n_xf = x.n_rep;
-    }
+    write_result(p, res);
+    if (l == 0) { res->xf_first = first; res->n_xf = x.n_rep; }
 }
 
 __global__ __launch_bounds__(64) void plan_kernel_xf(PlanParams Q) {
@@ -1631,45 +1198,11 @@ __global__ __launch_bounds__(64) void plan_kernel_xf(PlanParams Q) {
     const PlanDesc pd = Q.docs[d];
     PlanResult *res = Q.results + d;
     if (pd.skip) return;
-    const uint32_t A = U(pd.n_agents);
     P p;
-    p.erec = Q.erec + pd.erec_off;
-    p.par = Q.par + pd.par_off;
-    p.pent = Q.pent + pd.par_off;
-    p.pch = Q.pch + pd.par_off;
-    p.pcnt = Q.pcnt + pd.par_off;
-    p.child = Q.child + pd.child_off;
-    p.opc = Q.opc + pd.op_off;
-    p.doff = Q.doff + pd.doff_off;
-    p.dense = Q.dense + pd.dense_off;
-    p.tip = Q.tip + pd.tip_off * 2;
-    p.ne = U(pd.ne);
-    p.A = A;
-    p.ntip = U(pd.ntip);
-    p.n_lv = U(pd.n_lv);
-    // LDS: the todo stack, the pending bytes
-    XS x;
-    x.n_rep = 0;
-    x.rep = 0;
-    p.todo = lds16;
-    p.pending = reinterpret_cast<uint8_t *>(lds16 + PLAN_TODO_CAP);
-    p.base = nullptr;
-    p.prow = Q.prow + pd.prow_off;
-    p.order = nullptr;
-    p.walk = nullptr;
-    p.row_stride = pd.row_stride;
-    p.cmds = Q.cmds + pd.cmd_off;
-    p.tlist = Q.tlist + pd.tlist_off;
-    p.count_only = Q.count_only;
-    p.ccap = Q.count_only ? 0xFFFFFFFFu : U(pd.ccap);
-    p.tcap = Q.count_only ? 0xFFFFFFFFu : U(pd.tcap);
-    p.nc = p.nt = p.err = 0;
-    p.steps = 0;
-    p.limit = uint32_t(min<uint64_t>(2048ull * (uint64_t(p.ne) + 16) + 4ull * pd.n_lv + 4ull * uint64_t(pd.n_from) * pd.n_from + (1u << 20), 0xFFFFFFF0ull));
-    p.n_ret = p.n_adv = 0;
-    p.prof = Q.prof;
+    bind_doc(p, Q, pd, lds16, 2048ull * (uint64_t(pd.ne) + 16) + 4ull * pd.n_lv + 4ull * uint64_t(pd.n_from) * pd.n_from + (1u << 20));
+    XS x{0, 0};
     res->n_tip = 0;
-    if (p.ne > Q.lds_entries || A > 64 || p.ne == 0) {
+    if (p.ne > Q.lds_entries || p.A > 64 || p.ne == 0) {
         if (lane() == 0) res->status = PLAN_ERR_INTERNAL;
         return;
     }
@@ -1679,7 +1212,7 @@ __global__ __launch_bounds__(64) void plan_kernel_xf(PlanParams Q) {
 }  // namespace pdev
 
 int launch_walk(const PlanParams &q, void *stream, bool csr) {
-    if (!q.n_docs || !q.split || !q.walk) return OK;
+    if (!q.n_docs) return OK;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const size_t cap = q.todo_cap ? q.todo_cap : PLAN_TODO_CAP;
     if (cap > PLAN_TODO_CAP || (cap & 1u)) return ErrArg;
@@ -1703,9 +1236,8 @@ int launch_plan(const PlanParams &q, void *stream, bool walk) {
         hipLaunchKernelGGL(pdev::plan_kernel_xf, dim3(q.n_docs), dim3(64), lds, s, q);
         return launch_error() == hipSuccess ? OK : ErrHip;
     }
-    if (walk && q.split && q.walk && launch_walk(q, stream, false)) return ErrHip;
-    if (q.split) hipLaunchKernelGGL(pdev::plan_kernel_1<true>, dim3(q.n_docs), dim3(64), lds, s, q);
-    else hipLaunchKernelGGL(pdev::plan_kernel_1<false>, dim3(q.n_docs), dim3(64), lds, s, q);
+    if (walk && launch_walk(q, stream, false)) return ErrHip;
+    hipLaunchKernelGGL(pdev::plan_kernel_1, dim3(q.n_docs), dim3(64), lds, s, q);
     if (launch_error() != hipSuccess) return ErrHip;
     if (q.max_agents > 64) {
         hipLaunchKernelGGL(pdev::plan_kernel_wide, dim3(q.n_docs), dim3(64), lds, s, q);

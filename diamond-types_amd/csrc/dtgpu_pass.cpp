@@ -47,7 +47,7 @@ Pipe list_pipe(const dtgpu_batch *B, hipStream_t s, const uint32_t *list, uint32
     return p;
 }
 bool walk_beside(const dtgpu_batch *B, const Pipe &p) {
-    return B->dec && B->n_gpu_planned && p.prep.chain_flag && !p.prep.check && p.plan.walk && p.plan.coff && p.w &&
+    return B->dec && B->n_gpu_planned && p.prep.chain_flag && !p.prep.check && p.plan.coff && p.w &&
            B->cfg.walk_overlap;
 }
 // The prep half; `mid` (nullable) is recorded at its end on s.
@@ -59,9 +59,9 @@ int pipe_prep(dtgpu_batch *B, const Pipe &p, hipEvent_t mid) {
         if (launch_cut(p.cut, s)) return ErrHip;   // (after prep: it reads the parents' entries)
         return mid && hipEventRecord(mid, s) != hipSuccess ? ErrHip : OK;
     }
-    // the walk reads prep's CSR and, split, the planner only the entry records' heads
+    // the walk reads prep's CSR and the planner only the entry records' heads
     PrepParams pp = p.prep;
-    pp.short_rec = p.plan.split ? 1u : 0u;
+    pp.short_rec = 1;
     if (launch_prep_stage(pp, s, 1) || hop(p.w0, s, p.w)) return ErrHip;
     if (launch_walk(p.plan, p.w, true) != OK) return ErrHip;
     if (hipEventRecord(p.w1, p.w) != hipSuccess) return ErrHip;

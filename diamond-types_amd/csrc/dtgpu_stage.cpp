@@ -43,8 +43,6 @@ Settings settings_for(const dtgpu_batch_opts *o) {
     num("DTGPU_LATE_FROM", 1, UINT64_MAX, c.late_from);
     num("DTGPU_LDS_FILL", 1, UINT64_MAX, c.lds_fill);
     on("DTGPU_FLAT", c.flat);
-    on("DTGPU_PLAN_SPLIT", c.plan_split);
-    on("DTGPU_PLAN_WALK", c.plan_walk);
     on("DTGPU_PREP_CHAINS", c.prep_chains);
     on("DTGPU_CRITICAL", c.critical);
     on("DTGPU_PRIO", c.prio);
@@ -209,8 +207,7 @@ dtgpu_status size_plans(dtgpu_batch &B, const std::vector<PlanDesc> &pdesc, uint
     q.child = B.p_child.p; q.opc = B.p_opc.p;
     q.aruns = B.d_aruns.p; q.tip = B.p_tip.p; q.erec = B.p_erec.p; q.doff = B.p_doff.p;
     q.dense = B.p_dense.p; q.base = B.p_base.p; q.order = B.p_order.p;
-    q.walk = B.cfg.plan_walk ? B.p_walk.p : nullptr;
-    q.split = B.cfg.plan_split ? 1u : 0u;
+    q.walk = B.p_walk.p;
     q.lds_entries = (lds_entries + 7) & ~7u;
     q.max_agents = max_agents;
     q.prof = B.cfg.plan_prof ? 1u : 0u;
@@ -221,7 +218,7 @@ dtgpu_status size_plans(dtgpu_batch &B, const std::vector<PlanDesc> &pdesc, uint
     q.count_only = 0;
     pres.resize(n);
     CK(hipMemcpyAsync(pres.data(), B.p_results.p, std::max<size_t>(n, 1) * sizeof(PlanResult), hipMemcpyDeviceToHost, s));
-    if (wres && q.walk) {
+    if (wres) {
         wres->resize(2 * n);
         CK(hipMemcpyAsync(wres->data(), q.walk, 2 * n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     }
@@ -926,7 +923,7 @@ dtgpu_status stage_device(dtgpu_decoded *dec, const dtgpu_batch_opts *opts, dtgp
     // here (plus slack), not PLAN_TODO_CAP -- the walk kernel's LDS then leaves room for the
     // chain decomposition's waves beside it.  (A deeper walk would fail its document visibly,
     // PLAN_TODO_FULL; the walk is deterministic, so none does.)
-    if (q.walk && q.split && !xf) {
+    if (!xf) {
         uint32_t deep = 0;
         for (size_t i = 0; i < n; i++)
             if (!pdesc[i].skip && pres[i].status == PLAN_OK) deep = std::max(deep, wres[2 * i] >> 16);
