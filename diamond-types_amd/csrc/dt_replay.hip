@@ -124,7 +124,8 @@ template <int L> DEV uint32_t ix(const uint32_t *p) {
 template <int L> DEV uint32_t ix16(const uint16_t *p) { return *p; }
 
 enum ProfSlot { P_INS = 0, P_DEL, P_TOG, P_MAT, P_YJS, P_SPLIT, P_FIND, P_BLOAD, P_ORR, P_RUN, P_R1, P_R2, P_R3, P_N_YJS, P_N_SPLIT,
-                P_T1, P_T2, P_T3, P_N_DIRTY, P_N_LOAD, P_N };   // P_T*: retreat/advance pass split (entries + merge, counts, index)
+                P_T1, P_T2, P_T3, P_N_DIRTY, P_N_LOAD, P_N_LOOK, P_N_SKIP, P_N };   // P_T*: retreat/advance pass split (entries + merge, counts, index)
+                                                                   // P_N_LOOK / P_N_SKIP: position lookups, and those the cached block answered
 
 struct Doc {
     // inputs
@@ -159,12 +160,22 @@ struct Doc {
     // same state (every change is stored); a toggle touching the block drops it.
     uint32_t cb, cit;
     u64 cmv, cml;
+    // flat tier: the visible items before block cb (PRE_NONE: unknown, or no cached block) and
+    // cb's position in ord[].  An edit whose position falls among cb's visible items skips the
+    // index scan (find_vis); a retreat/advance pass that leaves cb cached adds the flips in
+    // blocks before it to cpre.
+    uint32_t cpre, cpos;
     // transformed-ops mode (iter_xf_operations): per block the never-deleted mask, per top
     // position the never-deleted total, per LV the transformed position written out
     u64 *mup;
     uint32_t *tup;
     uint32_t *xf;
 };
+
+// An unknown prefix is so large that no position's rank in the cached block (pos - cpre,
+// unsigned) falls below the block's visible count: the hit test needs no validity flag.
+constexpr uint32_t PRE_NONE = 0x80000000u;
+DEV bool pre_known(uint32_t pre) { return int32_t(pre) >= 0; }
 
 DEV void fail(Doc &D, uint32_t code, uint32_t site) {
     if (!D.err) { D.err = code; D.site = site; }
@@ -268,6 +279,7 @@ struct Found {
     uint32_t b, k;     // block, rank of the item among the block's visible items
     uint32_t S, tp;    // its superblock and that superblock's top position
     uint32_t c;        // the block's packed counts (flat index), NONE: not gathered
+    uint32_t p;        // the block's position in ord[] (flat index)
 };
 template <int L>
 DEV bool find_vis(Doc &D, uint32_t p, Found &f) {
@@ -297,6 +309,7 @@ DEV bool find_vis(Doc &D, uint32_t p, Found &f) {
         f.b = U(rdl(b, fl));
         f.k = U(p - base - rdl(inc - v, fl));
         f.c = U(rdl(w, fl));
+        f.p = (S << 6) + fl;
         return true;
     }
     for (uint32_t c = 0; c < D.nsb; c += 64) {
@@ -570,7 +583,11 @@ DEV uint32_t up_rank(Doc &D, uint32_t b, uint32_t s) {
 template <int L, bool PROF, bool XF>
 DEV void insert_run(Doc &D, uint32_t b, uint32_t s, uint32_t it, u64 mv, u64 ml, uint32_t lv, uint32_t k,
                     uint32_t ol, uint32_t orr, uint32_t tph, uint32_t c_in) {
+    // flat tier: the caller set D.cpre / D.cpos for b.  They stay true of the block the run ends
+    // in if that is b: a split puts the new block after b.
+    constexpr bool PC = L == IX_FLAT && !XF;
     D.cb = NONE;
+    const uint32_t b_in = b;
     const uint32_t l = lane();
     const uint32_t lv0 = lv, k0 = k;
     if (XF) {   // the run's items land at consecutive upstream positions
@@ -666,6 +683,7 @@ DEV void insert_run(Doc &D, uint32_t b, uint32_t s, uint32_t it, u64 mv, u64 ml,
         s += m;
     }
     D.cb = b; D.cit = it; D.cmv = mv; D.cml = ml;   // block state after the run
+    if (PC && b != b_in) D.cpre = PRE_NONE;
     const uint64_t t3 = tick<PROF>();
     for (uint32_t j0 = 0; j0 < k0; j0 += 64) {   // wave-uniform loop, masked store
         const uint32_t j = j0 + l, nit = lv0 + j;
@@ -814,16 +832,32 @@ DEV void do_insert(Doc &D, uint32_t lv, uint32_t k, uint32_t pos) {
     uint64_t tp = tick<PROF>();
     uint32_t b, kk = 0, tph = 0;   // tph: top position of b's superblock (first block: 0)
     uint32_t fcnt = NONE;          // b's packed counts when the lookup gathered them
+    constexpr bool PC = L == IX_FLAT && !XF;   // the cached block answers lookups that land in it
+    // PC: cpre / cpos are set here for the block the lookup returns (a hit leaves them as they
+    // are); the rare ways the run ends in another block (YjsMod moved it, a split) forget cpre
     if (pos == 0) {
         b = first_block<L>(D);
+        if (PC) { D.cpre = 0; D.cpos = 0; }
     } else {
-        Found f;
-        if (!find_vis<L>(D, pos - 1, f)) { fail(D, ErrCheckout, 13); return; }
-        b = f.b;
-        kk = f.k;
-        tph = f.tp;
-        fcnt = f.c;
+        // item pos - 1 is in the cached block iff its rank there is below the block's visible count
+        const uint32_t rk = pos - 1 - D.cpre;
+        const uint32_t hit = PC ? U(uint32_t(rk < uint32_t(__popcll(D.cmv)))) : 0u;
+        if (hit) {
+            b = D.cb;
+            kk = rk;
+            tph = D.cpos >> 6;
+        } else {
+            Found f;
+            if (!find_vis<L>(D, pos - 1, f)) { fail(D, ErrCheckout, 13); return; }
+            b = f.b;
+            kk = f.k;
+            tph = f.tp;
+            fcnt = f.c;
+            if (PC) { D.cpre = pos - 1 - f.k; D.cpos = f.p; }
+        }
+        if (PC && PROF) D.prof[P_N_SKIP] += hit;
     }
+    if (PC && PROF) D.prof[P_N_LOOK]++;   // every insert and delete round resolves one position
     if (PROF) { const uint64_t t = tick<PROF>(); D.prof[P_FIND] += t - tp; tp = t; }
     const uint32_t c0 = L == IX_FLAT && fcnt != NONE ? fcnt : U(ix<L>(D.cnt + b));
     const uint32_t bc = c_items(c0);
@@ -882,6 +916,7 @@ DEV void do_insert(Doc &D, uint32_t lv, uint32_t k, uint32_t pos) {
             else load_block<L, PROF>(D, b, cb, it, mv, ml);
             cb &= ~C_DIRTY;
             tph = NONE;
+            if (PC) D.cpre = PRE_NONE;   // (the items before the new block are not counted)
         }
         if (PROF) { const uint64_t t = tick<PROF>(); D.prof[P_YJS] += t - tp; tp = t; D.prof[P_N_YJS]++; }
     }
@@ -898,8 +933,20 @@ DEV void do_delete(Doc &D, uint32_t lv, uint32_t n, uint32_t pos, bool fwd) {
     uint32_t j0 = 0;
     uint32_t up_done = 0;   // XF: never-deleted items this run deleted in earlier (left) blocks
     while (j0 < n) {   // each round deletes >= 1 item or fails
+        constexpr bool PC = L == IX_FLAT && !XF;   // as in do_insert
         Found f;
-        if (!find_vis<L>(D, pos, f)) { fail(D, ErrCheckout, 14); return; }
+        const uint32_t rk = pos - D.cpre;
+        const uint32_t hit = PC ? U(uint32_t(rk < uint32_t(__popcll(D.cmv)))) : 0u;
+        if (hit) {   // (cpre = pos - rk and cpos stay)
+            f.b = D.cb;
+            f.k = rk;
+            f.tp = D.cpos >> 6;
+            f.c = NONE;
+        } else {
+            if (!find_vis<L>(D, pos, f)) { fail(D, ErrCheckout, 14); return; }
+            if (PC) { D.cpre = pos - f.k; D.cpos = f.p; }
+        }
+        if (PC && PROF) { D.prof[P_N_LOOK]++; D.prof[P_N_SKIP] += hit; }
         const uint32_t b = f.b, kk = f.k, tpos = f.tp;
         const uint32_t c0 = L == IX_FLAT && f.c != NONE ? f.c : U(ix<L>(D.cnt + b));
         uint32_t it;
@@ -1055,14 +1102,18 @@ DEV void toggle_pass(Doc &D, uint32_t off, uint32_t n, uint32_t pre, bool have_p
         }
         if (BALLOT(bad)) { fail(D, ErrCheckout, 16); return; }
         const bool flip = fv || fl;
-        if (BALLOT(flip && b == D.cb)) D.cb = NONE;
+        if (BALLOT(flip && b == D.cb)) { D.cb = NONE; if (L == IX_FLAT) D.cpre = PRE_NONE; }
         if (PROF) { const uint64_t t = tick<PROF>(); D.prof[P_T2] += t - tq; tq = t; }
         if (L == IX_FLAT) {   // flat LDS index: the chunk's packed totals in one atomic
+            uint32_t pb = NONE;   // the flipping lane's block position
             if (flip) {
-                at_add(D.top + (uint32_t(D.opos16[b]) >> 6), uint32_t(dv) + (uint32_t(dl) << 16));
+                pb = D.opos16[b];
+                at_add(D.top + (pb >> 6), uint32_t(dv) + (uint32_t(dl) << 16));
                 at_add(D.cnt + b, uint32_t(dv) * C_VIS + uint32_t(dl) * C_LIVE);
                 at_or(D.cnt + b, C_DIRTY);
             }
+            // the cached block stays: visibility flips in blocks before it move its prefix
+            if (pre_known(D.cpre)) D.cpre += U(wave_sum(pb < D.cpos ? uint32_t(dv) : 0u));
         } else if (L) {   // LDS index: per-lane LDS atomics
             if (flip) {
                 const uint32_t tp = ix<L>(D.sbpos + (opos_of<L>(D, b) >> 6));
@@ -1166,14 +1217,18 @@ DEV void toggle_pass_1(Doc &D, uint32_t off, uint32_t n, uint32_t pre, bool have
     const int32_t dv = fv ? (nc == 1 ? 1 : -1) : 0;
     const int32_t dl = fl ? (nc != 0 ? 1 : -1) : 0;
     const bool flip = fv || fl;
-    if (BALLOT(flip && b == D.cb)) D.cb = NONE;
+    if (BALLOT(flip && b == D.cb)) { D.cb = NONE; if (L == IX_FLAT) D.cpre = PRE_NONE; }
     if (PROF) { const uint64_t t = tick<PROF>(); D.prof[P_T2] += t - tq; tq = t; }
     if (L == IX_FLAT) {   // flat LDS index: the chunk's packed totals in one atomic
+        uint32_t pb = NONE;   // the flipping lane's block position
         if (flip) {
-            at_add(D.top + (uint32_t(D.opos16[b]) >> 6), uint32_t(dv) + (uint32_t(dl) << 16));
+            pb = D.opos16[b];
+            at_add(D.top + (pb >> 6), uint32_t(dv) + (uint32_t(dl) << 16));
             at_add(D.cnt + b, uint32_t(dv) * C_VIS + uint32_t(dl) * C_LIVE);
             at_or(D.cnt + b, C_DIRTY);
         }
+        // the cached block stays: visibility flips in blocks before it move its prefix
+        if (pre_known(D.cpre)) D.cpre += U(wave_sum(pb < D.cpos ? uint32_t(dv) : 0u));
     } else if (L) {   // LDS index: per-lane LDS atomics
         if (flip) {
             const uint32_t tp = ix<L>(D.sbpos + (opos_of<L>(D, b) >> 6));
@@ -1596,6 +1651,16 @@ DEV uint32_t check_invariants(Doc &D, DocResult *res) {
         for (uint32_t c = nlists + l; c < D.max_sb; c += 64)
             if (BALLOT(D.top[c] != 0)) return 211;
     }
+    if (L == IX_FLAT && !XF && D.cb != NONE && pre_known(D.cpre)) {   // the cached block's position and visible prefix
+        if (D.cb >= D.nb || U(D.opos16[D.cb]) != D.cpos) return 212;
+        uint32_t before = 0;
+        for (uint32_t q0 = 0; q0 < D.cpos; q0 += 64) {
+            const uint32_t q = q0 + l;
+            before += wave_sum(q < D.cpos ? c_vis(D.cnt[D.sbl[min(q, D.nb - 1)]]) : 0u);
+        }
+        if (U(before) != D.cpre) return 212;
+        if (uint32_t(__popcll(D.cmv)) != c_vis(U(D.cnt[D.cb]))) return 213;
+    }
     return 0;
 }
 
@@ -1635,6 +1700,8 @@ DEV void run_doc(Doc &D) {
     D.cb = NONE;
     D.cit = 0;
     D.cmv = D.cml = 0;
+    D.cpre = PRE_NONE;
+    D.cpos = 0;
     if (PROF) for (int i = 0; i < P_N; i++) D.prof[i] = 0;
     const uint64_t t_start = tick<PROF>();
     // commands are fetched 64 at a time (one per lane) and broadcast with readlane; the first
@@ -1733,6 +1800,8 @@ DEV void run_doc(Doc &D) {
             for (int i = P_T1; i < P_N_DIRTY; i++) res->dbg[16 + (i - P_T1)] = uint32_t(D.prof[i] >> 4);
             res->dbg[19] = uint32_t(D.prof[P_N_DIRTY]);
             res->dbg[20] = uint32_t(D.prof[P_N_LOAD]);
+            res->dbg[21] = uint32_t(D.prof[P_N_LOOK]);
+            res->dbg[22] = uint32_t(D.prof[P_N_SKIP]);
         }
     }
 }

@@ -590,6 +590,16 @@ dtgpu_status dtgpu_batch_doc_stats(dtgpu_batch *B, size_t i, uint32_t out[29]) {
     out[28] = r.dbg[20];   // block loads (not from the registers' cached block)
     return DTGPU_OK;
 }
+dtgpu_status dtgpu_batch_lookup_stats(dtgpu_batch *B, size_t i, uint32_t out[2]) {
+    if (!B || i >= B->docs.size() || !out) return DTGPU_ERR_ARG;
+    DocResult r;
+    if (hipMemcpyAsync(&r, B->d_results.p + i, sizeof r, hipMemcpyDeviceToHost, B->stream) != hipSuccess ||
+        hipStreamSynchronize(B->stream) != hipSuccess)
+        return DTGPU_ERR_HIP;
+    out[0] = r.dbg[21];   // position lookups (inserts past position 0, delete rounds)
+    out[1] = r.dbg[22];   // those the cached block answered
+    return DTGPU_OK;
+}
 uint64_t dtgpu_batch_total_lv(const dtgpu_batch *B) { return B ? B->total_lv : 0; }
 
 dtgpu_status dtgpu_batch_results(dtgpu_batch *B, dtgpu_doc_result *res) {

@@ -188,6 +188,7 @@ def lib():
     L.dtgpu_batch_algorithmic_bytes.argtypes = [vp]
     L.dtgpu_batch_algorithmic_bytes.restype = u64
     L.dtgpu_batch_doc_stats.argtypes = [vp, sz, ctypes.POINTER(ctypes.c_uint32)]
+    L.dtgpu_batch_lookup_stats.argtypes = [vp, sz, ctypes.POINTER(ctypes.c_uint32)]
     L.dtgpu_batch_segments.argtypes = [vp, sz, ctypes.POINTER(ctypes.c_uint32), sz]
     L.dtgpu_batch_segments.restype = sz
     L.dtgpu_oplog_cut_ranges.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), sz]
@@ -1016,7 +1017,11 @@ class Batch:
                 "cyc_ins", "cyc_del", "cyc_tog", "cyc_mat", "cyc_yjs", "cyc_split", "cyc_find", "cyc_bload",
                 "cyc_orr", "cyc_run", "cyc_r1", "cyc_r2", "cyc_r3", "n_yjs", "n_split", "cyc_total",
                 "n_sb", "lds_index", "cyc_t1", "cyc_t2", "cyc_t3", "n_dirty", "n_load"]
-        return dict(zip(keys, list(out)))
+        st = dict(zip(keys, list(out)))
+        look = (ctypes.c_uint32 * 2)()   # position lookups, and those the cached block answered
+        _check(lib().dtgpu_batch_lookup_stats(self._h, i, look))
+        st["n_lookup"], st["n_lookup_skip"] = look[0], look[1]
+        return st
 
     def segments(self, i):
         """Cut replay: the LV segments document i replayed as (see dtgpu_batch_segments), as

@@ -354,6 +354,10 @@ uint64_t dtgpu_batch_algorithmic_bytes(dtgpu_batch *batch);
  * cut documents' later segments in staging order, up to the first index that returns
  * DTGPU_ERR_ARG. */
 dtgpu_status dtgpu_batch_doc_stats(dtgpu_batch *batch, size_t doc, uint32_t out[29]);
+/* DTGPU_DEBUG=2, flat LDS tier: out[0] the position lookups of document `doc`'s inserts and
+ * delete rounds in the last run, out[1] those the block cached in registers answered without
+ * the index scan.  Addresses documents and segments as dtgpu_batch_doc_stats does. */
+dtgpu_status dtgpu_batch_lookup_stats(dtgpu_batch *batch, size_t doc, uint32_t out[2]);
 /* Cut replay: the LV segments document `doc` replays as, each on its own wave -- cut where the
  * whole history below the cut is one version that every later op has seen, the boundary the
  * reference fast-forwards across (src/listmerge/merge.rs:811-840), each later segment starting

@@ -32,7 +32,7 @@ def main():
         parts = " ".join(f"{k[4:]}={v / 1e6:.2f}M({100 * v / tot:.0f}%)" for k, v in cyc.items())
         print(f"{name}x{copies}: status={res['status']} ms={ms:.2f} cmds={st['n_cmds']} items={st['n_items']} "
               f"blocks={st['n_blocks']}/{st['max_blocks']} sb={st['n_sb']} lds={st['lds_index']} yjs={st['n_yjs']} splits={st['n_split']} "
-              f"loads={st['n_load']} dirty={st['n_dirty']} {parts}",
+              f"loads={st['n_load']} dirty={st['n_dirty']} lookups={st['n_lookup']} skipped={st['n_lookup_skip']} {parts}",
               flush=True)
         for k, s in enumerate(b.segments(0)):   # cut replay: one wave per segment
             print(f"  segment {k}: lv [{s['lo']}, {s['hi'] if s['hi'] != 0xFFFFFFFF else 'end'}) "
