@@ -8,6 +8,8 @@
 #include <cstdlib>
 #include <vector>
 
+#include "../../include/dtgpu.h"
+
 namespace dtgpu {
 
 template <typename T>
@@ -38,6 +40,8 @@ inline bool hip_failed(hipError_t e, const char *file, int line) {
     return true;
 }
 #define DTGPU_HIP_FAILED(x) ::dtgpu::hip_failed((x), __FILE__, __LINE__)
+// In a function that returns dtgpu_status (or an int it converts to): leave on a failed HIP call.
+#define DTGPU_CK(x) do { if (DTGPU_HIP_FAILED(x)) return DTGPU_ERR_HIP; } while (0)
 
 // Staging phase clock (DTGPU_STAGE_PROF=1): stage_prof("name") prints the wall milliseconds since
 // the previous call on this thread to stderr; stage_prof(nullptr) restarts the clock.

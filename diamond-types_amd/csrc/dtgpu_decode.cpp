@@ -1,4 +1,6 @@
-// dtgpu_decode.cpp -- C ABI of the batched GPU `.dt` decoder (include/dtgpu.h, dtgpu_decode_*).
+// dtgpu_decode.cpp -- C ABI of the batched GPU `.dt` decoder (include/dtgpu.h, dtgpu_decode_*):
+// create / run, the two calls that make a new resident handle from one (dtgpu_decode_add,
+// dtgpu_decode_history; the request scaffold is dt_request.hpp), export and status.
 //
 // Staging: the documents are packed into one HBM arena (256-B aligned, 256 B of padding each so
 // the decoder's register windows never read past the allocation), a sizing pass of the decode
@@ -20,47 +22,11 @@
 #include "dt_history.hpp"
 #include "dt_host.hpp"
 #include "dt_merge.hpp"
-#include "dt_patch.hpp"
 #include "dt_request.hpp"
 
 using namespace dtgpu;
 
-// dtgpu_decode_encode_from's result: the patches in one HBM arena (owned), each request's reduced
-// frontier, status and length
-struct dtgpu_patches {
-    int device = 0;
-    size_t n = 0;
-    float mark_ms = 0, build_ms = 0;
-    std::vector<PatchResult> res;
-    std::vector<uint32_t> n_front, form;
-    std::vector<uint64_t> out_off;
-    DevBuf<uint32_t> front;
-    DevBuf<uint8_t> out;
-};
-
 namespace {
-
-uint32_t multmodp_host(uint32_t a, uint32_t b) {
-    if (!a) return 0;
-    uint32_t m = 1u << 31, p = 0;
-    for (;;) {
-        if (a & m) {
-            p ^= b;
-            if ((a & (m - 1)) == 0) break;
-        }
-        m >>= 1;
-        b = (b & 1u) ? (b >> 1) ^ 0x82F63B78u : b >> 1;
-    }
-    return p;
-}
-
-// x^(2^k) mod the CRC-32C polynomial, k < 32: the table the kernels' CRC segment combine reads
-void crc_x2n(uint32_t (&x2n)[32]) {
-    x2n[0] = 1u << 30;
-    for (int k = 1; k < 32; k++) x2n[k] = multmodp_host(x2n[k - 1], x2n[k - 1]);
-}
-
-uint64_t align256(uint64_t x) { return (x + 255) & ~uint64_t(255); }
 
 // SoA bytes of one decoded document: 16 B per op run and agent run, 8 per entry (+4 per CSR slot),
 // 4 per parent, the inserted bytes and 4 per LV of content offsets
@@ -91,13 +57,9 @@ Status upload_packed(uint8_t *dst, uint64_t total, const uint8_t *const *docs, c
     for (int k = 0; k < 2; k++)
         if (!st.buf[k] && DTGPU_HIP_FAILED(hipHostMalloc(reinterpret_cast<void **>(&st.buf[k]), kStageChunk, hipHostMallocPortable)))
             return ErrHip;
-    struct Ev {   // this upload's copy-done events, one per chunk
-        hipEvent_t e[2] = {nullptr, nullptr};
-        bool rec[2] = {false, false};
-        ~Ev() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-    } ev;
-    for (int k = 0; k < 2; k++)
-        if (DTGPU_HIP_FAILED(hipEventCreateWithFlags(&ev.e[k], hipEventDisableTiming))) return ErrHip;
+    Events<2> ev;   // this upload's copy-done events, one per chunk
+    bool rec[2] = {false, false};
+    if (DTGPU_HIP_FAILED(ev.create(hipEventDisableTiming))) return ErrHip;
     auto end_of = [&](size_t i) { return i + 1 < n ? desc[i + 1].in_off : total; };
     size_t i = 0;
     int k = 0;
@@ -113,7 +75,7 @@ Status upload_packed(uint8_t *dst, uint64_t total, const uint8_t *const *docs, c
             i++;
             continue;
         }
-        if (ev.rec[k] && DTGPU_HIP_FAILED(hipEventSynchronize(ev.e[k]))) return ErrHip;   // the chunk's last copy is done
+        if (rec[k] && DTGPU_HIP_FAILED(hipEventSynchronize(ev.e[k]))) return ErrHip;   // the chunk's last copy is done
         uint8_t *chunk = st.buf[k];
         std::atomic<size_t> next{i};
         auto work = [&] {
@@ -129,16 +91,127 @@ Status upload_packed(uint8_t *dst, uint64_t total, const uint8_t *const *docs, c
         work();
         for (auto &th : pool) th.join();
         if (DTGPU_HIP_FAILED(hipMemcpyAsync(dst + base, chunk, end_of(j - 1) - base, hipMemcpyHostToDevice, s)) ||
-            DTGPU_HIP_FAILED(hipEventRecord(ev.e[k], s)))
+            DTGPU_HIP_FAILED(ev.record(k, s)))
             return ErrHip;
-        ev.rec[k] = true;
+        rec[k] = true;
         k ^= 1;
         i = j;
     }
     return DTGPU_HIP_FAILED(hipStreamSynchronize(s)) ? ErrHip : OK;
 }
 
+// A new handle's device, stream and timing events.
+dtgpu_status open_handle(dtgpu_decoded &D) {
+    DTGPU_CK(hipSetDevice(D.device));
+    DTGPU_CK(hipStreamCreateWithFlags(&D.stream, hipStreamNonBlocking));
+    DTGPU_CK(hipEventCreate(&D.ev0));
+    DTGPU_CK(hipEventCreate(&D.ev1));
+    return DTGPU_OK;
+}
+
 }  // namespace
+
+// ListOpLog::checkout(&[LV]) for a batch, up to the replay (dt_history.hip): output i is the history
+// of a version of resident document doc[i] as an oplog of its own, in a new handle.  Staging: the
+// request CSR goes to HBM, the mark launch sizes every output (exact LVs and content bytes, upper
+// bounds for the run arrays), the arenas are laid out from its counts and the emit launch fills them.
+dtgpu_status dtgpu::decode_history(const dtgpu_decoded *B, const uint32_t *doc, const uint64_t *versions,
+                                   const size_t *version_off, size_t n, float *ms, dtgpu_decoded **out, HistKeep *keep) {
+    if (!out || !request_ok(B, doc, versions, version_off, n)) return DTGPU_ERR_ARG;
+    auto M = new dtgpu_decoded();
+    std::unique_ptr<dtgpu_decoded> guard(M);
+    M->device = B->device;
+    M->merged = true;
+    if (dtgpu_status e = open_handle(*M)) return e;
+    Events<2> ev;   // the emit launch's (the mark launch's are the handle's)
+    DTGPU_CK(ev.create());
+    hipStream_t s = M->stream;
+    M->n = n;
+    M->desc.assign(n, DecodeDesc{});
+    M->res.assign(n, DecodeResult{});
+    MarkSetup setup;
+    mark_setup(*B, doc, n, setup);
+    std::vector<HistDesc> &hd = setup.hd;
+    std::vector<uint32_t> req;
+    pack_sets(versions, version_off, n, req, hd.data(), &HistDesc::req_off, &HistDesc::n_req);
+    DevBuf<uint32_t> d_req, d_scr;
+    DevBuf<HistDesc> d_hd;
+    DTGPU_CK(d_req.upload(req, s));
+    DTGPU_CK(d_scr.alloc(setup.scr_words));
+    DTGPU_CK(d_hd.upload(hd, s));
+    DTGPU_CK(M->d_res.alloc(n));
+    DTGPU_CK(M->ver.alloc(uint64_t(DECODE_MAX_FRONTIER) * n));
+    DTGPU_CK(M->hfr.alloc(uint64_t(DECODE_MAX_FRONTIER) * n));
+    HistParams H{};
+    hist_params_base(*B, H);
+    H.req = d_req.p; H.scr = d_scr.p; H.o_ver = M->ver.p; H.o_front = M->hfr.p;
+    H.docs = d_hd.p; H.results = M->d_res.p; H.n_docs = uint32_t(n); H.lds_entries = setup.lds_entries;
+    H.keep_entries = keep ? 1u : 0u;
+    DTGPU_CK(hipEventRecord(M->ev0, s));
+    if (launch_hist_mark(H, s)) return DTGPU_ERR_HIP;
+    DTGPU_CK(hipEventRecord(M->ev1, s));
+    if (n) DTGPU_CK(hipMemcpyAsync(M->res.data(), M->d_res.p, n * sizeof(DecodeResult), hipMemcpyDeviceToHost, s));
+    DTGPU_CK(hipStreamSynchronize(s));
+    // the output arenas, from the mark launch's counts
+    uint64_t in = 0, ar = 0, ops = 0, ent = 0, poff = 0, par = 0, content = 0, lv = 0, ag = 0;
+    for (size_t i = 0; i < n; i++) {
+        const DecodeResult &r = M->res[i];
+        HistDesc &h = hd[i];
+        DecodeDesc &md = M->desc[i];
+        if (r.status) h.skip = r.status;
+        const bool ok = h.skip == 0;
+        h.c_arun = ok ? r.n_aruns : 0; h.c_op = ok ? r.n_ops : 0; h.c_ent = ok ? r.n_entries : 0; h.c_par = ok ? r.n_parents : 0;
+        h.c_content = ok ? r.n_content : 0; h.c_lv = ok ? uint32_t(r.n_lv) : 0; h.c_agent = ok ? h.b_n_agents : 0;
+        h.c_in = ok ? h.b_in_len : 0;
+        h.o_in = in; in = align256(in + h.c_in + 256);
+        h.o_arun = ar; ar += h.c_arun;
+        h.o_op = ops; ops += h.c_op;
+        h.o_ent = ent; ent += h.c_ent;
+        h.o_poff = poff; poff += h.c_ent + 1;
+        h.o_par = par; par += h.c_par;
+        h.o_content = content; content += h.c_content;
+        h.o_lv = lv; lv += h.c_lv;
+        h.o_agent = ag; ag += h.c_agent;
+        md.in_off = h.o_in; md.in_len = h.c_in;
+        md.arun_off = h.o_arun; md.op_off = h.o_op; md.ent_off = h.o_ent; md.poff_off = h.o_poff; md.par_off = h.o_par;
+        md.content_off = h.o_content; md.lv_off = h.o_lv; md.agent_off = h.o_agent; md.ver_off = h.o_ver;
+        md.arun_cap = h.c_arun; md.op_cap = h.c_op; md.ent_cap = h.c_ent; md.par_cap = h.c_par;
+        md.content_cap = h.c_content; md.lv_cap = h.c_lv; md.agent_cap = h.c_agent;
+    }
+    DTGPU_CK(M->in.alloc(in)); DTGPU_CK(M->aruns.alloc(4 * ar)); DTGPU_CK(M->ops.alloc(4 * ops)); DTGPU_CK(M->ent.alloc(2 * ent));
+    DTGPU_CK(M->poff.alloc(poff)); DTGPU_CK(M->par.alloc(par)); DTGPU_CK(M->content.alloc(content)); DTGPU_CK(M->cbyte.alloc(lv));
+    DTGPU_CK(M->agents.alloc(2 * ag));
+    DTGPU_CK(hipMemsetAsync(M->in.p, 0, std::max<uint64_t>(in, 1), s));
+    DTGPU_CK(d_hd.upload(hd, s));
+    H.docs = d_hd.p;
+    H.o_in = M->in.p; H.o_content = M->content.p; H.o_aruns = M->aruns.p; H.o_ops = M->ops.p; H.o_ent = M->ent.p;
+    H.o_poff = M->poff.p; H.o_par = M->par.p; H.o_cbyte = M->cbyte.p; H.o_agents = M->agents.p;
+    DTGPU_CK(ev.record(0, s));
+    if (launch_hist_emit(H, s)) return DTGPU_ERR_HIP;
+    DTGPU_CK(ev.record(1, s));
+    if (n) DTGPU_CK(hipMemcpyAsync(M->res.data(), M->d_res.p, n * sizeof(DecodeResult), hipMemcpyDeviceToHost, s));
+    DTGPU_CK(hipStreamSynchronize(s));
+    DTGPU_CK(fetch_frontiers(M->fronts, M->hfr.p, n));
+    float t0 = 0, t1 = 0;
+    DTGPU_CK(hipEventElapsedTime(&t0, M->ev0, M->ev1));
+    DTGPU_CK(ev.ms(0, 1, &t1));
+    M->last_ms = t0 + t1;
+    if (ms) *ms = t0 + t1;
+    for (size_t i = 0; i < n; i++) {
+        DecodeResult &r = M->res[i];
+        if (r.status == 0) M->in_bytes += soa_bytes(B->res[doc[i]]);   // read: the base document's arrays
+        r.prof[1] = uint32_t(t0 * 1000.f);   // the launches' microseconds, with the mark form in prof[0]
+        r.prof[2] = uint32_t(t1 * 1000.f);
+        M->fronts.status[i] = r.status;
+        M->fronts.n_front[i] = r.status == 0 ? r.n_version : 0u;
+    }
+    if (keep) {
+        std::swap(keep->scr.p, d_scr.p); std::swap(keep->scr.n, d_scr.n);
+        std::swap(keep->hd.p, d_hd.p); std::swap(keep->hd.n, d_hd.n);
+    }
+    *out = guard.release();
+    return DTGPU_OK;
+}
 
 extern "C" {
 
@@ -151,11 +224,7 @@ dtgpu_status dtgpu_decode_create(const uint8_t *const *docs, const size_t *lens,
     auto D = new dtgpu_decoded();
     std::unique_ptr<dtgpu_decoded> guard(D);
     D->device = opts ? opts->device : 0;
-#define CK(x) do { if (DTGPU_HIP_FAILED(x)) return DTGPU_ERR_HIP; } while (0)
-    CK(hipSetDevice(D->device));
-    CK(hipStreamCreateWithFlags(&D->stream, hipStreamNonBlocking));
-    CK(hipEventCreate(&D->ev0));
-    CK(hipEventCreate(&D->ev1));
+    if (dtgpu_status e = open_handle(*D)) return e;
     hipStream_t s = D->stream;
     D->n = n;
     D->desc.assign(n, DecodeDesc{});
@@ -174,14 +243,14 @@ dtgpu_status dtgpu_decode_create(const uint8_t *const *docs, const size_t *lens,
         // (only each document's padding is zeroed) and each chunk is copied while the next one is
         // packed -- no transient host copy of the whole batch (at 10k friendsforever documents a
         // 360 MB buffer spent ~100 ms in page faults and unmapping alone)
-        CK(D->in.alloc(total));
+        DTGPU_CK(D->in.alloc(total));
         int nt = opts && opts->host_threads > 0 ? opts->host_threads : int(std::thread::hardware_concurrency());
         nt = int(std::max<size_t>(1, std::min<size_t>({size_t(std::max(nt, 1)), size_t(16), n / 64 + 1})));
         if (Status e = upload_packed(D->in.p, total, docs, lens, n, D->desc, nt, s)) return dtgpu_status(e);
         stage_prof("decode: upload documents");
     }
-    CK(D->d_desc.upload(D->desc, s));
-    CK(D->d_res.alloc(n));
+    DTGPU_CK(D->d_desc.upload(D->desc, s));
+    DTGPU_CK(D->d_res.alloc(n));
     DecodeParams &P = D->P;
     P.in = D->in.p;
     P.docs = D->d_desc.p;
@@ -193,8 +262,8 @@ dtgpu_status dtgpu_decode_create(const uint8_t *const *docs, const size_t *lens,
     P.max_file_agents = 0;
     P.lz_ring = 0;
     if (launch_decode(P, s)) return DTGPU_ERR_HIP;
-    CK(hipMemcpyAsync(D->res.data(), D->d_res.p, n * sizeof(DecodeResult), hipMemcpyDeviceToHost, s));
-    CK(hipStreamSynchronize(s));
+    DTGPU_CK(hipMemcpyAsync(D->res.data(), D->d_res.p, n * sizeof(DecodeResult), hipMemcpyDeviceToHost, s));
+    DTGPU_CK(hipStreamSynchronize(s));
     stage_prof("decode: sizing pass");
     if (getenv("DTGPU_STAGE_PROF") && n) {   // core cycles per sizing phase: header + LZ4 claim, chunks, OpVersions
         double a[3] = {0, 0, 0}, m[3] = {0, 0, 0};
@@ -260,24 +329,24 @@ dtgpu_status dtgpu_decode_create(const uint8_t *const *docs, const size_t *lens,
         }
     }
     if (!fill_doc.empty()) {
-        CK(D->fill.alloc(fill_words));
-        CK(D->fill_n.alloc(n));
-        CK(D->fill_doc.alloc(fill_doc.size()));
-        CK(hipMemcpyAsync(D->fill_doc.p, fill_doc.data(), fill_doc.size() * 4, hipMemcpyHostToDevice, s));
+        DTGPU_CK(D->fill.alloc(fill_words));
+        DTGPU_CK(D->fill_n.alloc(n));
+        DTGPU_CK(D->fill_doc.alloc(fill_doc.size()));
+        DTGPU_CK(hipMemcpyAsync(D->fill_doc.p, fill_doc.data(), fill_doc.size() * 4, hipMemcpyHostToDevice, s));
     }
-    CK(D->lz.alloc(lz));
-    CK(D->aruns.alloc(4 * ar));
-    CK(D->alist.alloc(4 * ar));
-    CK(D->pre.alloc(4 * pre));
-    CK(D->ops.alloc(4 * ops));
-    CK(D->ent.alloc(2 * ent));
-    CK(D->poff.alloc(poff));
-    CK(D->par.alloc(par));
-    CK(D->content.alloc(content));
-    CK(D->cbyte.alloc(lv));
-    CK(D->agents.alloc(2 * ag));
-    CK(D->ver.alloc(ver));
-    CK(D->d_desc.upload(D->desc, s));
+    DTGPU_CK(D->lz.alloc(lz));
+    DTGPU_CK(D->aruns.alloc(4 * ar));
+    DTGPU_CK(D->alist.alloc(4 * ar));
+    DTGPU_CK(D->pre.alloc(4 * pre));
+    DTGPU_CK(D->ops.alloc(4 * ops));
+    DTGPU_CK(D->ent.alloc(2 * ent));
+    DTGPU_CK(D->poff.alloc(poff));
+    DTGPU_CK(D->par.alloc(par));
+    DTGPU_CK(D->content.alloc(content));
+    DTGPU_CK(D->cbyte.alloc(lv));
+    DTGPU_CK(D->agents.alloc(2 * ag));
+    DTGPU_CK(D->ver.alloc(ver));
+    DTGPU_CK(D->d_desc.upload(D->desc, s));
     P.docs = D->d_desc.p;
     P.lz = D->lz.p;
     P.aruns = D->aruns.p; P.alist = D->alist.p; P.pre = D->pre.p; P.ops = D->ops.p;
@@ -297,8 +366,8 @@ dtgpu_status dtgpu_decode_create(const uint8_t *const *docs, const size_t *lens,
         std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) {
             return uint64_t(D->desc[a].in_len) + D->res[a].lz_len > uint64_t(D->desc[b].in_len) + D->res[b].lz_len;
         });
-        CK(D->order.alloc(n));
-        CK(hipMemcpyAsync(D->order.p, ord.data(), n * 4, hipMemcpyHostToDevice, s));
+        DTGPU_CK(D->order.alloc(n));
+        DTGPU_CK(hipMemcpyAsync(D->order.p, ord.data(), n * 4, hipMemcpyHostToDevice, s));
         P.order = D->order.p;
     }
     P.fill = fill_doc.empty() ? nullptr : D->fill.p;
@@ -317,10 +386,10 @@ dtgpu_status dtgpu_decode_create(const uint8_t *const *docs, const size_t *lens,
             if (!D->desc[i].skip && D->res[i].lz_len >= LZ_BIG) big.push_back(uint32_t(i));
         // longest blocks first: they are dispatched first, each to a CU of its own
         std::stable_sort(big.begin(), big.end(), [&](uint32_t a, uint32_t b) { return D->res[a].lz_len > D->res[b].lz_len; });
-        CK(D->lz_big.alloc(big.size()));
-        CK(hipMemcpyAsync(D->lz_big.p, big.data(), big.size() * 4, hipMemcpyHostToDevice, s));
-        CK(D->lz_pre.alloc(n));
-        CK(hipMemsetAsync(D->lz_pre.p, 0, n * 4, s));
+        DTGPU_CK(D->lz_big.alloc(big.size()));
+        DTGPU_CK(hipMemcpyAsync(D->lz_big.p, big.data(), big.size() * 4, hipMemcpyHostToDevice, s));
+        DTGPU_CK(D->lz_pre.alloc(n));
+        DTGPU_CK(hipMemsetAsync(D->lz_pre.p, 0, n * 4, s));
         P.lz_big = D->lz_big.p;
         P.lz_pre = D->lz_pre.p;
         P.n_big = uint32_t(big.size());
@@ -329,9 +398,8 @@ dtgpu_status dtgpu_decode_create(const uint8_t *const *docs, const size_t *lens,
         // git-makefile blocks take 55.6 ms on three (47.4 on two)
         P.lz3_max = getenv("DTGPU_LZ3_MAX") ? uint32_t(strtoul(getenv("DTGPU_LZ3_MAX"), nullptr, 10)) : 4096u;
     }
-    CK(hipStreamSynchronize(s));
+    DTGPU_CK(hipStreamSynchronize(s));
     stage_prof("decode: arenas");
-#undef CK
     *out = guard.release();
     return DTGPU_OK;
 }
@@ -365,11 +433,7 @@ dtgpu_status dtgpu_decode_add(const dtgpu_decoded *B, const uint8_t *const *patc
     std::unique_ptr<dtgpu_decoded> guard(M);
     M->device = B->device;
     M->merged = true;
-#define CK(x) do { if (DTGPU_HIP_FAILED(x)) return DTGPU_ERR_HIP; } while (0)
-    CK(hipSetDevice(M->device));
-    CK(hipStreamCreateWithFlags(&M->stream, hipStreamNonBlocking));
-    CK(hipEventCreate(&M->ev0));
-    CK(hipEventCreate(&M->ev1));
+    if (dtgpu_status e = open_handle(*M)) return e;
     hipStream_t s = M->stream;
     M->n = n;
     // the patches, packed like dtgpu_decode_create's documents
@@ -388,12 +452,12 @@ dtgpu_status dtgpu_decode_add(const dtgpu_decoded *B, const uint8_t *const *patc
         std::vector<uint8_t> host(ptotal, 0);
         for (size_t i = 0; i < n; i++)
             if (lens[i]) std::memcpy(host.data() + pd[i].in_off, patches[i], lens[i]);
-        CK(pin.upload(host, s));
+        DTGPU_CK(pin.upload(host, s));
     }
     DevBuf<DecodeDesc> d_pd;
     DevBuf<DecodeResult> d_pr;
-    CK(d_pd.upload(pd, s));
-    CK(d_pr.alloc(n));
+    DTGPU_CK(d_pd.upload(pd, s));
+    DTGPU_CK(d_pr.alloc(n));
     std::vector<DecodeResult> pr(n);
     {   // sizing pass over the patches
         DecodeParams P{};
@@ -403,8 +467,8 @@ dtgpu_status dtgpu_decode_add(const dtgpu_decoded *B, const uint8_t *const *patc
         P.n_docs = uint32_t(n);
         P.size_only = 1;
         if (launch_decode(P, s)) return DTGPU_ERR_HIP;
-        CK(hipMemcpyAsync(pr.data(), d_pr.p, n * sizeof(DecodeResult), hipMemcpyDeviceToHost, s));
-        CK(hipStreamSynchronize(s));
+        DTGPU_CK(hipMemcpyAsync(pr.data(), d_pr.p, n * sizeof(DecodeResult), hipMemcpyDeviceToHost, s));
+        DTGPU_CK(hipStreamSynchronize(s));
     }
     // merged arenas
     std::vector<AddDesc> ad(n, AddDesc{});
@@ -469,14 +533,14 @@ dtgpu_status dtgpu_decode_add(const dtgpu_decoded *B, const uint8_t *const *patc
         md.arun_cap = a.c_arun; md.op_cap = a.c_op; md.ent_cap = a.c_ent; md.par_cap = a.c_par;
         md.content_cap = a.c_content; md.lv_cap = a.c_lv; md.agent_cap = a.c_agent;
     }
-    CK(M->in.alloc(in)); CK(M->lz.alloc(lz)); CK(M->aruns.alloc(4 * ar)); CK(M->ops.alloc(4 * ops));
-    CK(M->ent.alloc(2 * ent)); CK(M->poff.alloc(poff)); CK(M->par.alloc(par)); CK(M->content.alloc(content));
-    CK(M->cbyte.alloc(lv)); CK(M->agents.alloc(2 * ag)); CK(M->ver.alloc(ver)); CK(M->ffr.alloc(ver));
+    DTGPU_CK(M->in.alloc(in)); DTGPU_CK(M->lz.alloc(lz)); DTGPU_CK(M->aruns.alloc(4 * ar)); DTGPU_CK(M->ops.alloc(4 * ops));
+    DTGPU_CK(M->ent.alloc(2 * ent)); DTGPU_CK(M->poff.alloc(poff)); DTGPU_CK(M->par.alloc(par)); DTGPU_CK(M->content.alloc(content));
+    DTGPU_CK(M->cbyte.alloc(lv)); DTGPU_CK(M->agents.alloc(2 * ag)); DTGPU_CK(M->ver.alloc(ver)); DTGPU_CK(M->ffr.alloc(ver));
     DevBuf<uint32_t> d_scr;
-    CK(d_scr.alloc(4 * scr));
+    DTGPU_CK(d_scr.alloc(4 * scr));
     DevBuf<AddDesc> d_ad;
-    CK(d_ad.upload(ad, s));
-    CK(M->d_res.alloc(n));
+    DTGPU_CK(d_ad.upload(ad, s));
+    DTGPU_CK(M->d_res.alloc(n));
     AddParams A{};
     A.b_in = B->in.p; A.b_content = B->content.p; A.p_in = pin.p;
     A.b_aruns = B->aruns.p; A.b_ops = B->ops.p; A.b_ent = B->ent.p; A.b_poff = B->poff.p; A.b_par = B->par.p;
@@ -486,430 +550,44 @@ dtgpu_status dtgpu_decode_add(const dtgpu_decoded *B, const uint8_t *const *patc
     A.m_cbyte = M->cbyte.p; A.m_agents = M->agents.p; A.m_ver = M->ver.p; A.m_ffr = M->ffr.p; A.scr = d_scr.p;
     A.docs = d_ad.p; A.results = M->d_res.p; A.n_docs = uint32_t(n); A.max_file_agents = max_f; A.max_agents = max_a;
     crc_x2n(A.x2n);
-    CK(hipEventRecord(M->ev0, s));
+    DTGPU_CK(hipEventRecord(M->ev0, s));
     if (launch_decode_add(A, s)) return DTGPU_ERR_HIP;
-    CK(hipEventRecord(M->ev1, s));
+    DTGPU_CK(hipEventRecord(M->ev1, s));
     M->res.assign(n, DecodeResult{});
-    CK(hipMemcpyAsync(M->res.data(), M->d_res.p, n * sizeof(DecodeResult), hipMemcpyDeviceToHost, s));
-    CK(hipStreamSynchronize(s));
+    DTGPU_CK(hipMemcpyAsync(M->res.data(), M->d_res.p, n * sizeof(DecodeResult), hipMemcpyDeviceToHost, s));
+    DTGPU_CK(hipStreamSynchronize(s));
+    DTGPU_CK(fetch_frontiers(M->fronts, M->ffr.p, n));   // (m_ver = DECODE_MAX_FRONTIER * i)
     float t = 0;
-    CK(hipEventElapsedTime(&t, M->ev0, M->ev1));
+    DTGPU_CK(hipEventElapsedTime(&t, M->ev0, M->ev1));
     M->last_ms = t;
     if (ms) *ms = t;
-#undef CK
     // each merged document is valid (the resident one again after a failed merge); the merge's
-    // own status is kept apart
-    M->add_status.assign(n, 0);
+    // own status is kept apart, with the patch's version where it merged
     for (size_t i = 0; i < n; i++) {
-        M->add_status[i] = M->res[i].status;
+        M->fronts.status[i] = M->res[i].status;
+        M->fronts.n_front[i] = M->res[i].status == 0 ? M->res[i].n_file_frontier : 0u;
         M->res[i].status = B->res[i].status;
     }
     *out = guard.release();
     return DTGPU_OK;
 }
 
+// A handle dtgpu_decode_add made (ffr allocated): any other, a history handle too, is DTGPU_ERR_ARG.
 dtgpu_status dtgpu_decode_add_result(const dtgpu_decoded *M, size_t i, uint64_t *frontier, size_t cap,
                                      size_t *n_frontier) {
-    if (!M || !M->merged || i >= M->n || (!frontier && cap)) return DTGPU_ERR_ARG;
-    const uint32_t st = M->add_status[i];
-    const size_t k = st == 0 ? M->res[i].n_file_frontier : 0;
-    if (n_frontier) *n_frontier = k;
-    if (k && cap) {
-        std::vector<uint32_t> f(k);
-        if (hipMemcpy(f.data(), M->ffr.p + M->desc[i].ver_off, k * 4, hipMemcpyDeviceToHost) != hipSuccess)
-            return DTGPU_ERR_HIP;
-        for (size_t j = 0; j < k && j < cap; j++) frontier[j] = f[j];
-    }
-    return dtgpu_status(st);
+    return M && M->merged && M->ffr.p ? M->fronts.read(i, frontier, cap, n_frontier) : DTGPU_ERR_ARG;
 }
 
-// ListOpLog::checkout(&[LV]) for a batch, up to the replay (dt_history.hip): output i is the history
-// of a version of resident document doc[i] as an oplog of its own, in a new handle.  Staging: the
-// request CSR goes to HBM, the mark launch sizes every output (exact LVs and content bytes, upper
-// bounds for the run arrays), the arenas are laid out from its counts and the emit launch fills them.
 dtgpu_status dtgpu_decode_history(const dtgpu_decoded *B, const uint32_t *doc, const uint64_t *versions,
                                   const size_t *version_off, size_t n, float *ms, dtgpu_decoded **out) {
-    return dtgpu::decode_history(B, doc, versions, version_off, n, ms, out, nullptr);
-}
-extern "C++" dtgpu_status dtgpu::decode_history(const dtgpu_decoded *B, const uint32_t *doc, const uint64_t *versions,
-                                                const size_t *version_off, size_t n, float *ms, dtgpu_decoded **out,
-                                                HistKeep *keep) {
-    if (!B || !out || (n && (!doc || !version_off))) return DTGPU_ERR_ARG;
-    if (!B->merged && !B->ran) return DTGPU_ERR_ARG;   // not decoded yet
-    for (size_t i = 0; i < n; i++)
-        if (doc[i] >= B->n || version_off[i + 1] < version_off[i]) return DTGPU_ERR_ARG;
-    const size_t n_req = n ? version_off[n] - version_off[0] : 0;
-    if (n_req && !versions) return DTGPU_ERR_ARG;
-    auto M = new dtgpu_decoded();
-    std::unique_ptr<dtgpu_decoded> guard(M);
-    M->device = B->device;
-    M->merged = true;
-#define CK(x) do { if (DTGPU_HIP_FAILED(x)) return DTGPU_ERR_HIP; } while (0)
-    CK(hipSetDevice(M->device));
-    CK(hipStreamCreateWithFlags(&M->stream, hipStreamNonBlocking));
-    CK(hipEventCreate(&M->ev0));
-    CK(hipEventCreate(&M->ev1));
-    struct Ev {
-        hipEvent_t e[2] = {nullptr, nullptr};
-        ~Ev() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-    } ev;
-    CK(hipEventCreate(&ev.e[0]));
-    CK(hipEventCreate(&ev.e[1]));
-    hipStream_t s = M->stream;
-    M->n = n;
-    M->desc.assign(n, DecodeDesc{});
-    M->res.assign(n, DecodeResult{});
-    // the mark words of an output live in LDS up to this many base entries, in its HBM scratch
-    // past it (DTGPU_HISTORY_LDS_ENTRIES lowers the limit; 0: always HBM)
-    uint32_t lds_cap = HIST_LDS_ENTRIES;
-    const uint32_t lds_form = getenv("DTGPU_MARK_AGENT_FENCE") ? 2u : 1u;   // (measurement: the sweep's earlier fence)
-    if (const char *e = getenv("DTGPU_HISTORY_LDS_ENTRIES")) lds_cap = uint32_t(std::min<unsigned long>(strtoul(e, nullptr, 10), HIST_LDS_ENTRIES));
-    std::vector<HistDesc> hd(n, HistDesc{});
-    std::vector<uint32_t> req(n_req);
-    uint64_t scr = 0;
-    uint32_t lds_entries = 0;
-    for (size_t i = 0; i < n; i++) {
-        const DecodeDesc &bd = B->desc[doc[i]];
-        const DecodeResult &br = B->res[doc[i]];
-        HistDesc &h = hd[i];
-        h.skip = br.status;
-        h.b_in = bd.in_off; h.b_arun = bd.arun_off; h.b_op = bd.op_off; h.b_ent = bd.ent_off; h.b_poff = bd.poff_off;
-        h.b_par = bd.par_off; h.b_content = bd.content_off; h.b_lv = bd.lv_off; h.b_agent = bd.agent_off;
-        if (br.status == 0) {
-            h.b_in_len = bd.in_len; h.b_n_aruns = br.n_aruns; h.b_n_ops = br.n_ops; h.b_n_ent = br.n_entries;
-            h.b_n_par = br.n_parents; h.b_n_content = br.n_content; h.b_n_agents = br.n_agents;
-            h.b_n_lv = uint32_t(std::min<uint64_t>(br.n_lv, 0xFFFFFFFFull)); h.b_complete = br.content_complete;
-        }
-        h.req_off = version_off[i] - version_off[0];
-        h.n_req = uint32_t(version_off[i + 1] - version_off[i]);
-        for (size_t k = version_off[i]; k < version_off[i + 1]; k++)
-            req[k - version_off[0]] = uint32_t(std::min<uint64_t>(versions[k], 0xFFFFFFFFull));
-        h.use_lds = h.b_n_ent <= lds_cap ? lds_form : 0u;
-        if (h.use_lds && !h.skip) lds_entries = std::max(lds_entries, h.b_n_ent);
-        h.scr_off = scr;
-        scr += uint64_t(HIST_ENT_WORDS) * h.b_n_ent;
-        h.o_ver = uint64_t(DECODE_MAX_FRONTIER) * i;
-    }
-    DevBuf<uint32_t> d_req, d_scr;
-    DevBuf<HistDesc> d_hd;
-    CK(d_req.upload(req, s));
-    CK(d_scr.alloc(scr));
-    CK(d_hd.upload(hd, s));
-    CK(M->d_res.alloc(n));
-    CK(M->ver.alloc(uint64_t(DECODE_MAX_FRONTIER) * n));
-    CK(M->hfr.alloc(uint64_t(DECODE_MAX_FRONTIER) * n));
-    HistParams H{};
-    H.b_in = B->in.p; H.b_content = B->content.p; H.b_aruns = B->aruns.p; H.b_ops = B->ops.p; H.b_ent = B->ent.p;
-    H.b_poff = B->poff.p; H.b_par = B->par.p; H.b_cbyte = B->cbyte.p; H.b_agents = B->agents.p;
-    H.req = d_req.p; H.scr = d_scr.p; H.o_ver = M->ver.p; H.o_front = M->hfr.p;
-    H.docs = d_hd.p; H.results = M->d_res.p; H.n_docs = uint32_t(n); H.lds_entries = lds_entries;
-    H.keep_entries = keep ? 1u : 0u;
-    CK(hipEventRecord(M->ev0, s));
-    if (launch_hist_mark(H, s)) return DTGPU_ERR_HIP;
-    CK(hipEventRecord(M->ev1, s));
-    if (n) CK(hipMemcpyAsync(M->res.data(), M->d_res.p, n * sizeof(DecodeResult), hipMemcpyDeviceToHost, s));
-    CK(hipStreamSynchronize(s));
-    // the output arenas, from the mark launch's counts
-    uint64_t in = 0, ar = 0, ops = 0, ent = 0, poff = 0, par = 0, content = 0, lv = 0, ag = 0;
-    for (size_t i = 0; i < n; i++) {
-        const DecodeResult &r = M->res[i];
-        HistDesc &h = hd[i];
-        DecodeDesc &md = M->desc[i];
-        if (r.status) h.skip = r.status;
-        const bool ok = h.skip == 0;
-        h.c_arun = ok ? r.n_aruns : 0; h.c_op = ok ? r.n_ops : 0; h.c_ent = ok ? r.n_entries : 0; h.c_par = ok ? r.n_parents : 0;
-        h.c_content = ok ? r.n_content : 0; h.c_lv = ok ? uint32_t(r.n_lv) : 0; h.c_agent = ok ? h.b_n_agents : 0;
-        h.c_in = ok ? h.b_in_len : 0;
-        h.o_in = in; in = align256(in + h.c_in + 256);
-        h.o_arun = ar; ar += h.c_arun;
-        h.o_op = ops; ops += h.c_op;
-        h.o_ent = ent; ent += h.c_ent;
-        h.o_poff = poff; poff += h.c_ent + 1;
-        h.o_par = par; par += h.c_par;
-        h.o_content = content; content += h.c_content;
-        h.o_lv = lv; lv += h.c_lv;
-        h.o_agent = ag; ag += h.c_agent;
-        md.in_off = h.o_in; md.in_len = h.c_in;
-        md.arun_off = h.o_arun; md.op_off = h.o_op; md.ent_off = h.o_ent; md.poff_off = h.o_poff; md.par_off = h.o_par;
-        md.content_off = h.o_content; md.lv_off = h.o_lv; md.agent_off = h.o_agent; md.ver_off = h.o_ver;
-        md.arun_cap = h.c_arun; md.op_cap = h.c_op; md.ent_cap = h.c_ent; md.par_cap = h.c_par;
-        md.content_cap = h.c_content; md.lv_cap = h.c_lv; md.agent_cap = h.c_agent;
-    }
-    CK(M->in.alloc(in)); CK(M->aruns.alloc(4 * ar)); CK(M->ops.alloc(4 * ops)); CK(M->ent.alloc(2 * ent));
-    CK(M->poff.alloc(poff)); CK(M->par.alloc(par)); CK(M->content.alloc(content)); CK(M->cbyte.alloc(lv));
-    CK(M->agents.alloc(2 * ag));
-    CK(hipMemsetAsync(M->in.p, 0, std::max<uint64_t>(in, 1), s));
-    CK(d_hd.upload(hd, s));
-    H.docs = d_hd.p;
-    H.o_in = M->in.p; H.o_content = M->content.p; H.o_aruns = M->aruns.p; H.o_ops = M->ops.p; H.o_ent = M->ent.p;
-    H.o_poff = M->poff.p; H.o_par = M->par.p; H.o_cbyte = M->cbyte.p; H.o_agents = M->agents.p;
-    CK(hipEventRecord(ev.e[0], s));
-    if (launch_hist_emit(H, s)) return DTGPU_ERR_HIP;
-    CK(hipEventRecord(ev.e[1], s));
-    if (n) CK(hipMemcpyAsync(M->res.data(), M->d_res.p, n * sizeof(DecodeResult), hipMemcpyDeviceToHost, s));
-    CK(hipStreamSynchronize(s));
-    float t0 = 0, t1 = 0;
-    CK(hipEventElapsedTime(&t0, M->ev0, M->ev1));
-    CK(hipEventElapsedTime(&t1, ev.e[0], ev.e[1]));
-#undef CK
-    M->last_ms = t0 + t1;
-    if (ms) *ms = t0 + t1;
-    M->add_status.assign(n, 0);
-    for (size_t i = 0; i < n; i++) {
-        DecodeResult &r = M->res[i];
-        if (r.status == 0) M->in_bytes += soa_bytes(B->res[doc[i]]);   // read: the base document's arrays
-        r.prof[1] = uint32_t(t0 * 1000.f);   // the launches' microseconds, with the mark form in prof[0]
-        r.prof[2] = uint32_t(t1 * 1000.f);
-        M->add_status[i] = r.status;
-    }
-    if (keep) {
-        std::swap(keep->scr.p, d_scr.p); std::swap(keep->scr.n, d_scr.n);
-        std::swap(keep->hd.p, d_hd.p); std::swap(keep->hd.n, d_hd.n);
-    }
-    *out = guard.release();
-    return DTGPU_OK;
+    return decode_history(B, doc, versions, version_off, n, ms, out, nullptr);
 }
 
+// A history handle (hfr allocated): a plain decoded or a merged handle is DTGPU_ERR_ARG.
 dtgpu_status dtgpu_decode_history_result(const dtgpu_decoded *H, size_t i, uint64_t *frontier, size_t cap,
                                          size_t *n_frontier) {
-    if (!H || !H->hfr.p || i >= H->n || (!frontier && cap)) return DTGPU_ERR_ARG;
-    const uint32_t st = H->res[i].status;
-    const size_t k = st == 0 ? H->res[i].n_version : 0;
-    if (n_frontier) *n_frontier = k;
-    if (k && cap) {
-        std::vector<uint32_t> f(k);
-        if (hipMemcpy(f.data(), H->hfr.p + H->desc[i].ver_off, k * 4, hipMemcpyDeviceToHost) != hipSuccess)
-            return DTGPU_ERR_HIP;
-        for (size_t j = 0; j < k && j < cap; j++) frontier[j] = f[j];
-    }
-    return dtgpu_status(st);
+    return H && H->hfr.p ? H->fronts.read(i, frontier, cap, n_frontier) : DTGPU_ERR_ARG;
 }
-
-// ListOpLog::encode_from(opts, from) for a batch (dt_patch.hip).  Staging as dtgpu_decode_history:
-// the request CSR goes to HBM, the mark launch reduces every request and counts its patch, each
-// request's scratch and output are laid out from those counts (patch_words / patch_bytes and the
-// byte bound below), and the build launch writes the files.
-dtgpu_status dtgpu_decode_encode_from(const dtgpu_decoded *B, const uint32_t *doc, const uint64_t *versions,
-                                      const size_t *version_off, size_t n, uint32_t flags, float *ms,
-                                      dtgpu_patches **out) {
-    if (out) *out = nullptr;
-    if (!B || !out || (n && (!doc || !version_off))) return DTGPU_ERR_ARG;
-    if (!B->merged && !B->ran) return DTGPU_ERR_ARG;   // not decoded yet
-    if (flags & ~uint32_t(DTGPU_ENCODE_FULL)) return DTGPU_ERR_ARG;
-    for (size_t i = 0; i < n; i++)
-        if (doc[i] >= B->n || version_off[i + 1] < version_off[i]) return DTGPU_ERR_ARG;
-    const size_t n_req = n ? version_off[n] - version_off[0] : 0;
-    if (n_req && !versions) return DTGPU_ERR_ARG;
-#define CK(x) do { if (DTGPU_HIP_FAILED(x)) return DTGPU_ERR_HIP; } while (0)
-    CK(hipSetDevice(B->device));
-    struct Own {
-        hipStream_t s = nullptr;
-        ~Own() { if (s) (void)hipStreamDestroy(s); }
-    } own;
-    CK(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking));
-    MarkSetup setup;
-    mark_setup(*B, doc, n, setup);
-    std::vector<uint32_t> req(n_req);
-    for (size_t i = 0; i < n; i++) {
-        HistDesc &h = setup.hd[i];
-        h.req_off = version_off[i] - version_off[0];
-        h.n_req = uint32_t(version_off[i + 1] - version_off[i]);
-        for (size_t k = version_off[i]; k < version_off[i + 1]; k++)
-            req[k - version_off[0]] = uint32_t(std::min<uint64_t>(versions[k], 0xFFFFFFFFull));
-    }
-    DevBuf<uint32_t> d_req;
-    DevBuf<HistDesc> d_hd;
-    CK(d_req.upload(req, own.s));
-    CK(d_hd.upload(setup.hd, own.s));
-#undef CK
-    return patches_from_requests(B, doc, n, flags, setup, d_hd.p, d_req.p, own.s, ms, out);
-}
-
-extern "C++" {
-namespace dtgpu {
-
-void hist_params_base(const dtgpu_decoded &B, HistParams &H) {
-    H.b_in = B.in.p; H.b_content = B.content.p; H.b_aruns = B.aruns.p; H.b_ops = B.ops.p; H.b_ent = B.ent.p;
-    H.b_poff = B.poff.p; H.b_par = B.par.p; H.b_cbyte = B.cbyte.p; H.b_agents = B.agents.p;
-}
-
-void mark_setup(const dtgpu_decoded &B, const uint32_t *doc, size_t n, MarkSetup &ms) {
-    ms.hd.assign(n, HistDesc{});
-    ms.scr_words = 0;
-    ms.lds_entries = 0;
-    // the mark sweep's words: in LDS or in HBM scratch, by the history projection's rule and override
-    uint32_t lds_cap = HIST_LDS_ENTRIES;
-    const uint32_t lds_form = getenv("DTGPU_MARK_AGENT_FENCE") ? 2u : 1u;   // (measurement: the sweep's earlier fence)
-    if (const char *e = getenv("DTGPU_HISTORY_LDS_ENTRIES")) lds_cap = uint32_t(std::min<unsigned long>(strtoul(e, nullptr, 10), HIST_LDS_ENTRIES));
-    for (size_t i = 0; i < n; i++) {
-        const DecodeDesc &bd = B.desc[doc[i]];
-        const DecodeResult &br = B.res[doc[i]];
-        HistDesc &h = ms.hd[i];
-        h.skip = br.status;
-        h.b_in = bd.in_off; h.b_arun = bd.arun_off; h.b_op = bd.op_off; h.b_ent = bd.ent_off; h.b_poff = bd.poff_off;
-        h.b_par = bd.par_off; h.b_content = bd.content_off; h.b_lv = bd.lv_off; h.b_agent = bd.agent_off;
-        if (br.status == 0) {
-            h.b_in_len = bd.in_len; h.b_n_aruns = br.n_aruns; h.b_n_ops = br.n_ops; h.b_n_ent = br.n_entries;
-            h.b_n_par = br.n_parents; h.b_n_content = br.n_content; h.b_n_agents = br.n_agents;
-            h.b_n_lv = uint32_t(std::min<uint64_t>(br.n_lv, 0xFFFFFFFFull)); h.b_complete = br.content_complete;
-        }
-        h.use_lds = h.b_n_ent <= lds_cap ? lds_form : 0u;
-        if (h.use_lds && !h.skip) ms.lds_entries = std::max(ms.lds_entries, h.b_n_ent);
-        h.scr_off = ms.scr_words;
-        ms.scr_words += uint64_t(HIST_ENT_WORDS) * h.b_n_ent;
-        h.o_ver = uint64_t(DECODE_MAX_FRONTIER) * i;
-    }
-}
-
-dtgpu_status patches_from_requests(const dtgpu_decoded *B, const uint32_t *doc, size_t n, uint32_t flags,
-                                   const MarkSetup &setup, const HistDesc *d_hd, const uint32_t *d_req, hipStream_t s,
-                                   float *ms, dtgpu_patches **out, MarkOut *mark) {
-    const std::vector<HistDesc> &hd = setup.hd;
-    auto M = new dtgpu_patches();
-    std::unique_ptr<dtgpu_patches> guard(M);
-    M->device = B->device;
-    M->n = n;
-#define CK(x) do { if (DTGPU_HIP_FAILED(x)) return DTGPU_ERR_HIP; } while (0)
-    struct Own {
-        hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-        ~Own() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-    } own;
-    for (hipEvent_t &e : own.e) CK(hipEventCreate(&e));
-    DevBuf<uint32_t> d_scr, d_ver, d_w;
-    DevBuf<uint8_t> d_b;
-    DevBuf<PatchDesc> d_pd;
-    DevBuf<PatchCounts> d_cnt;
-    DevBuf<PatchResult> d_res;
-    CK(d_scr.alloc(setup.scr_words));
-    CK(d_ver.alloc(uint64_t(DECODE_MAX_FRONTIER) * n));
-    CK(M->front.alloc(uint64_t(DECODE_MAX_FRONTIER) * n));
-    CK(d_cnt.alloc(n));
-    CK(d_res.alloc(n));
-    PatchParams P{};
-    HistParams &H = P.H;
-    hist_params_base(*B, H);
-    H.req = d_req; H.scr = d_scr.p; H.o_ver = d_ver.p; H.o_front = M->front.p;
-    H.docs = d_hd; H.n_docs = uint32_t(n);
-    P.counts = d_cnt.p; P.results = d_res.p; P.n_docs = uint32_t(n); P.lds_entries = setup.lds_entries;
-    P.prof = getenv("DTGPU_PATCH_PROF") ? 1u : 0u;   // read at call time: the build waves count their phase cycles
-    P.flags = flags & (DTGPU_ENCODE_STORE_INSERTED_CONTENT | DTGPU_ENCODE_COMPRESS_CONTENT);
-    crc_x2n(P.x2n);
-    CK(hipEventRecord(own.e[0], s));
-    if (launch_patch_mark(P, s)) return DTGPU_ERR_HIP;
-    CK(hipEventRecord(own.e[1], s));
-    std::vector<PatchCounts> cnt(n, PatchCounts{});
-    if (n) CK(hipMemcpyAsync(cnt.data(), d_cnt.p, n * sizeof(PatchCounts), hipMemcpyDeviceToHost, s));
-    CK(hipStreamSynchronize(s));
-    // scratch and output of every request, from the mark launch's counts
-    std::vector<PatchDesc> pd(n, PatchDesc{});
-    M->out_off.assign(n, 0);
-    uint64_t words = 0, bytes = 0, outb = 0;
-    for (size_t i = 0; i < n; i++) {
-        const PatchCounts &c = cnt[i];
-        const DecodeResult &br = B->res[doc[i]];
-        PatchDesc &d = pd[i];
-        d.skip = c.status;
-        // the StartBranch content is the checkout at `from`: the host's dtgpu_oplog_encode has it
-        if (!d.skip && c.n_front && (flags & DTGPU_ENCODE_STORE_START_BRANCH_CONTENT)) d.skip = DECODE_DEFER;
-        if (d.skip) continue;
-        d.n_pieces = c.n_pieces; d.n_par = c.n_par; d.n_ar = c.n_ar; d.n_op = c.n_op; d.n_lv = c.n_lv;
-        d.n_text = c.n_text; d.n_front = c.n_front;
-        d.doc_id_off = br.doc_id_off; d.doc_id_len = br.doc_id_len;
-        // records: a ContentIsKnown change inside an op-run piece splits it (only where content is missing)
-        const uint64_t oprec = uint64_t(c.n_op) + (hd[i].b_complete ? 0 : c.n_lv);
-        // bytes: an agent assignment run is three varints of <= 5 bytes; a txn its length, then per
-        // parent <= 5 bytes (local) or <= 10 (foreign agent and seq), 1 for ROOT; an op run <= 12
-        // (a 36-bit head, a 33-bit diff); the Version two varints per frontier LV; the names chunk
-        // lists at most every agent; PATCH_FIXED_BYTES covers the magic, the chunk headers and the CRC
-        const uint64_t c_aa = 15ull * c.n_ar + 16, c_tx = 6ull * c.n_pieces + 10ull * c.n_par + 16;
-        const uint64_t doc_id = br.doc_id_len == 0xFFFFFFFFu ? 0 : br.doc_id_len;
-        const uint64_t cap = PATCH_FIXED_BYTES + patch_lz_bound(c.n_text) + c.n_names + doc_id + 10ull * c.n_front + c_aa + 12 * oprec + c_tx;
-        if (oprec > 0x7FFFFFFFull || cap > 0x7FFFFFFFull) { d = PatchDesc{}; d.skip = DTGPU_ERR_CAPACITY; continue; }
-        d.c_oprec = uint32_t(oprec); d.c_aa = uint32_t(c_aa); d.c_tx = uint32_t(c_tx); d.out_cap = uint32_t(cap);
-        d.w_off = words; words += patch_words(hd[i].b_n_ent, hd[i].b_n_agents, d);
-        d.b_off = bytes; bytes = (bytes + patch_bytes(d) + 15) & ~uint64_t(15);
-        d.out_off = outb; outb = align256(outb + cap);
-        M->out_off[i] = d.out_off;
-    }
-    CK(d_w.alloc(words));
-    CK(d_b.alloc(bytes));
-    CK(M->out.alloc(outb));
-    CK(d_pd.upload(pd, s));
-    P.docs = d_pd.p; P.w = d_w.p; P.b = d_b.p; P.out = M->out.p;
-    CK(hipEventRecord(own.e[2], s));
-    if (launch_patch_build(P, s)) return DTGPU_ERR_HIP;
-    CK(hipEventRecord(own.e[3], s));
-    M->res.assign(n, PatchResult{});
-    if (n) CK(hipMemcpyAsync(M->res.data(), d_res.p, n * sizeof(PatchResult), hipMemcpyDeviceToHost, s));
-    if (mark) {
-        mark->front.assign(size_t(DECODE_MAX_FRONTIER) * n, 0);
-        if (n) CK(hipMemcpyAsync(mark->front.data(), M->front.p, mark->front.size() * 4, hipMemcpyDeviceToHost, s));
-    }
-    CK(hipStreamSynchronize(s));
-    float t0 = 0, t1 = 0;
-    CK(hipEventElapsedTime(&t0, own.e[0], own.e[1]));
-    CK(hipEventElapsedTime(&t1, own.e[2], own.e[3]));
-#undef CK
-    M->n_front.assign(n, 0);
-    for (size_t i = 0; i < n; i++) M->n_front[i] = cnt[i].status ? 0u : cnt[i].n_front;
-    M->form.assign(n, 0);
-    for (size_t i = 0; i < n; i++) M->form[i] = cnt[i].form;
-    if (mark) {
-        mark->status.assign(n, 0);
-        for (size_t i = 0; i < n; i++) mark->status[i] = cnt[i].status;
-        mark->n_front = M->n_front;
-    }
-    M->mark_ms = t0;
-    M->build_ms = t1;
-    if (ms) *ms = t0 + t1;
-    *out = guard.release();
-    return DTGPU_OK;
-}
-
-}  // namespace dtgpu
-}  // extern "C++"
-
-size_t dtgpu_patches_size(const dtgpu_patches *p) { return p ? p->n : 0; }
-
-dtgpu_status dtgpu_patches_result(const dtgpu_patches *p, size_t i, uint64_t *frontier, size_t cap, size_t *n_frontier) {
-    if (n_frontier) *n_frontier = 0;
-    if (!p || i >= p->n || (!frontier && cap)) return DTGPU_ERR_ARG;
-    const size_t k = p->n_front[i];
-    if (n_frontier) *n_frontier = k;
-    if (k && cap) {
-        std::vector<uint32_t> f(k);
-        if (hipMemcpy(f.data(), p->front.p + uint64_t(DECODE_MAX_FRONTIER) * i, k * 4, hipMemcpyDeviceToHost) != hipSuccess)
-            return DTGPU_ERR_HIP;
-        for (size_t j = 0; j < k && j < cap; j++) frontier[j] = f[j];
-    }
-    return dtgpu_status(p->res[i].status);
-}
-
-dtgpu_status dtgpu_patches_get(const dtgpu_patches *p, size_t i, uint8_t *out, size_t cap, size_t *out_len) {
-    if (out_len) *out_len = 0;
-    if (!p || i >= p->n) return DTGPU_ERR_ARG;
-    const PatchResult &r = p->res[i];
-    if (r.status) return dtgpu_status(r.status);
-    if (out_len) *out_len = r.len;
-    if (!out) return DTGPU_OK;
-    if (cap < r.len) return DTGPU_ERR_ARG;
-    if (r.len && hipMemcpy(out, p->out.p + p->out_off[i], r.len, hipMemcpyDeviceToHost) != hipSuccess) return DTGPU_ERR_HIP;
-    return DTGPU_OK;
-}
-
-dtgpu_status dtgpu_patches_profile(const dtgpu_patches *p, size_t i, uint32_t out[12]) {
-    if (!p || i >= p->n || !out) return DTGPU_ERR_ARG;
-    const PatchResult &r = p->res[i];
-    out[0] = p->form[i];
-    out[1] = uint32_t(p->mark_ms * 1000.f);
-    out[2] = uint32_t(p->build_ms * 1000.f);
-    out[3] = r.n_walk;
-    for (int k = 0; k < 7; k++) out[4 + k] = r.cyc[k];
-    out[11] = 0;
-    return DTGPU_OK;
-}
-
-void dtgpu_patches_free(dtgpu_patches *p) { delete p; }
 
 size_t dtgpu_decode_size(const dtgpu_decoded *D) { return D ? D->n : 0; }
 

@@ -15,13 +15,14 @@
 
 #include "dt_batch.hpp"
 #include "dt_merge.hpp"
+#include "dt_request.hpp"
 
 using namespace dtgpu;
 
 struct dtgpu_merges {
     int device = 0;
     size_t n = 0;
-    std::vector<uint32_t> status, n_front, front;   // front: DECODE_MAX_FRONTIER words per request
+    FrontierSet fronts;                   // n_front: 0 for a failed request and for a ROOT one
     std::vector<uint32_t> n_rec, ncmd, first;
     std::vector<uint64_t> rec_off;
     DevBuf<uint32_t> rec;                 // every request's records, {base lv, pos}
@@ -36,23 +37,15 @@ dtgpu_status dtgpu_decode_xf_from(const dtgpu_decoded *base, const uint32_t *doc
                                   const size_t *from_off, const uint64_t *merging, const size_t *merging_off, size_t n,
                                   float *kernel_ms, dtgpu_merges **out) {
     if (out) *out = nullptr;
-    if (!base || !out || (n && (!docs || !from_off || !merging_off))) return DTGPU_ERR_ARG;
-    if (!base->merged && !base->ran) return DTGPU_ERR_ARG;   // not decoded yet
-    for (size_t i = 0; i < n; i++) {
-        if (docs[i] >= base->n || from_off[i + 1] < from_off[i] || merging_off[i + 1] < merging_off[i]) return DTGPU_ERR_ARG;
-        if ((from_off[i + 1] > from_off[i] && !from) || (merging_off[i + 1] > merging_off[i] && !merging)) return DTGPU_ERR_ARG;
-    }
-#define CK(x) do { if (DTGPU_HIP_FAILED(x)) return DTGPU_ERR_HIP; } while (0)
-    CK(hipSetDevice(base->device));
+    if (!out || !request_ok(base, docs, from, from_off, n) || !sets_ok(merging, merging_off, n)) return DTGPU_ERR_ARG;
+    DTGPU_CK(hipSetDevice(base->device));
     auto M = std::make_unique<dtgpu_merges>();
     M->device = base->device;
     M->n = n;
-    M->status.assign(n, 0);
-    M->n_front.assign(n, 0);
     M->n_rec.assign(n, 0); M->ncmd.assign(n, 0); M->first.assign(n, 0);
     M->rec_off.assign(n + 1, 0);
     if (kernel_ms) *kernel_ms = 0;
-    if (!n) { *out = M.release(); return DTGPU_OK; }
+    if (!n) { *out = M.release(); return DTGPU_OK; }   // (an empty FrontierSet)
 
     // ---- 1. the projections: Hist(from u merging) of every request -------------------------------
     std::vector<uint64_t> uni;
@@ -66,7 +59,7 @@ dtgpu_status dtgpu_decode_xf_from(const dtgpu_decoded *base, const uint32_t *doc
         uni_off[i + 1] = uni.size();
         root[i] = uni_off[i + 1] == uni_off[i];
         const size_t f0 = fb.size();
-        for (size_t k = from_off[i]; k < from_off[i + 1]; k++) fb.push_back(uint32_t(std::min<uint64_t>(from[k], 0xFFFFFFFFull)));
+        for (size_t k = from_off[i]; k < from_off[i + 1]; k++) fb.push_back(lv32(from[k]));
         std::sort(fb.begin() + ptrdiff_t(f0), fb.end());
         fb.erase(std::unique(fb.begin() + ptrdiff_t(f0), fb.end()), fb.end());
         fb_off[i + 1] = fb.size();
@@ -80,33 +73,30 @@ dtgpu_status dtgpu_decode_xf_from(const dtgpu_decoded *base, const uint32_t *doc
     }
     std::unique_ptr<dtgpu_decoded> hold(H);
     hipStream_t s = H->stream;
+    // the merged version is the projection's reduced request (H goes on into the batch without it)
+    M->fronts = std::move(H->fronts);
+    std::vector<uint32_t> &status = M->fronts.status, &n_front = M->fronts.n_front;
     std::vector<uint32_t> ok(n, 0);
     for (size_t i = 0; i < n; i++) {
-        M->status[i] = H->res[i].status;
-        if (M->status[i] == 0 && fb_off[i + 1] - fb_off[i] > MERGE_MAX_FROM) M->status[i] = DECODE_DEFER;
-        ok[i] = M->status[i] == 0 && !root[i] ? 1u : 0u;
-        M->n_front[i] = ok[i] ? H->res[i].n_version : 0u;
+        if (status[i] == 0 && fb_off[i + 1] - fb_off[i] > MERGE_MAX_FROM) status[i] = DECODE_DEFER;
+        ok[i] = status[i] == 0 && !root[i] ? 1u : 0u;
+        if (!ok[i]) n_front[i] = 0;
     }
-    M->front.assign(size_t(DECODE_MAX_FRONTIER) * n, 0);
-    CK(hipMemcpyAsync(M->front.data(), H->hfr.p, M->front.size() * 4, hipMemcpyDeviceToHost, s));
 
     // ---- 2. `from` in projected LVs ---------------------------------------------------------------
-    struct Ev {
-        hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-        ~Ev() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-    } ev;
-    for (hipEvent_t &e : ev.e) CK(hipEventCreate(&e));
+    Events<4> ev;
+    DTGPU_CK(ev.create());
     DevBuf<uint32_t> d_fb, d_ok;
     DevBuf<uint32_t> &d_fp = M->from_proj;
     DevBuf<uint64_t> d_fboff;
-    CK(d_fb.upload(fb, s)); CK(d_fp.alloc(fb.size())); CK(d_ok.upload(ok, s)); CK(d_fboff.upload(fb_off, s));
+    DTGPU_CK(d_fb.upload(fb, s)); DTGPU_CK(d_fp.alloc(fb.size())); DTGPU_CK(d_ok.upload(ok, s)); DTGPU_CK(d_fboff.upload(fb_off, s));
     MergeParams mp{};
     mp.b_ent = base->ent.p; mp.scr = keep.scr.p; mp.hd = keep.hd.p; mp.n = uint32_t(n);
     mp.from = d_fb.p; mp.from_out = d_fp.p; mp.from_off = d_fboff.p; mp.ok = d_ok.p;
-    CK(hipEventRecord(ev.e[0], s));
+    DTGPU_CK(ev.record(0, s));
     if (launch_merge_from(mp, s)) return DTGPU_ERR_HIP;
-    CK(hipEventRecord(ev.e[1], s));
-    CK(hipStreamSynchronize(s));
+    DTGPU_CK(ev.record(1, s));
+    DTGPU_CK(hipStreamSynchronize(s));
 
     // ---- 3. the transformed-ops batch over the projections ----------------------------------------
     XfStage xf;
@@ -138,7 +128,7 @@ dtgpu_status dtgpu_decode_xf_from(const dtgpu_decoded *base, const uint32_t *doc
     std::vector<uint64_t> cmd_off(n, 0), lv_off(n, 0);
     uint64_t total = 0;
     for (size_t i = 0; i < n; i++) {
-        if (ok[i] && dr[i].status != 0) { M->status[i] = dr[i].status; ok[i] = 0; M->n_front[i] = 0; }
+        if (ok[i] && dr[i].status != 0) { status[i] = dr[i].status; ok[i] = 0; n_front[i] = 0; }
         M->rec_off[i] = total;
         if (!ok[i]) continue;
         const DocDesc &d = B->docs[i];
@@ -147,23 +137,22 @@ dtgpu_status dtgpu_decode_xf_from(const dtgpu_decoded *base, const uint32_t *doc
         total += xf.n_xf[i];
     }
     M->rec_off[n] = total;
-    CK(M->rec.alloc(2 * total));
+    DTGPU_CK(M->rec.alloc(2 * total));
     DevBuf<uint64_t> d_coff, d_lvoff, d_roff;
     DevBuf<uint32_t> d_ncmd, d_first, d_nrec;
-    CK(d_coff.upload(cmd_off, s)); CK(d_lvoff.upload(lv_off, s)); CK(d_roff.upload(M->rec_off, s));
-    CK(d_ncmd.upload(M->ncmd, s)); CK(d_first.upload(M->first, s)); CK(d_nrec.upload(M->n_rec, s));
+    DTGPU_CK(d_coff.upload(cmd_off, s)); DTGPU_CK(d_lvoff.upload(lv_off, s)); DTGPU_CK(d_roff.upload(M->rec_off, s));
+    DTGPU_CK(d_ncmd.upload(M->ncmd, s)); DTGPU_CK(d_first.upload(M->first, s)); DTGPU_CK(d_nrec.upload(M->n_rec, s));
     mp.cmds = B->d_cmds.p; mp.xf = B->d_xf.p;
     mp.cmd_off = d_coff.p; mp.lv_off = d_lvoff.p; mp.rec_off = d_roff.p;
     mp.ncmd = d_ncmd.p; mp.first = d_first.p; mp.n_rec = d_nrec.p;
     mp.rec = M->rec.p;
-    CK(hipEventRecord(ev.e[2], s));
+    DTGPU_CK(ev.record(2, s));
     if (launch_merge_records(mp, s)) return DTGPU_ERR_HIP;
-    CK(hipEventRecord(ev.e[3], s));
-    CK(hipStreamSynchronize(s));
+    DTGPU_CK(ev.record(3, s));
+    DTGPU_CK(hipStreamSynchronize(s));
     float t0 = 0, t1 = 0;
-    CK(hipEventElapsedTime(&t0, ev.e[0], ev.e[1]));
-    CK(hipEventElapsedTime(&t1, ev.e[2], ev.e[3]));
-#undef CK
+    DTGPU_CK(ev.ms(0, 1, &t0));
+    DTGPU_CK(ev.ms(2, 3, &t1));
     M->us[0] = uint32_t(ms_hist * 1000.f);
     for (int k = 0; k < 3; k++) M->us[1 + k] = uint32_t(pass[k] * 1000.f);
     M->us[4] = uint32_t((t0 + t1) * 1000.f);
@@ -176,17 +165,13 @@ size_t dtgpu_merges_size(const dtgpu_merges *m) { return m ? m->n : 0; }
 
 dtgpu_status dtgpu_merges_result(const dtgpu_merges *m, size_t i, uint64_t *frontier, size_t cap, size_t *n_frontier) {
     if (n_frontier) *n_frontier = 0;
-    if (!m || i >= m->n || (!frontier && cap)) return DTGPU_ERR_ARG;
-    const size_t k = m->n_front[i];
-    if (n_frontier) *n_frontier = k;
-    for (size_t j = 0; j < k && j < cap; j++) frontier[j] = m->front[size_t(DECODE_MAX_FRONTIER) * i + j];
-    return dtgpu_status(m->status[i]);
+    return m ? m->fronts.read(i, frontier, cap, n_frontier) : DTGPU_ERR_ARG;
 }
 
 dtgpu_status dtgpu_merges_ops(const dtgpu_merges *m, size_t i, uint32_t *out, size_t cap, size_t *n_out) {
     if (n_out) *n_out = 0;
     if (!m || i >= m->n) return DTGPU_ERR_ARG;
-    if (m->status[i]) return dtgpu_status(m->status[i]);
+    if (m->fronts.status[i]) return dtgpu_status(m->fronts.status[i]);
     const size_t k = m->n_rec[i];
     if (n_out) *n_out = k;
     if (!out) return DTGPU_OK;
@@ -199,8 +184,8 @@ dtgpu_status dtgpu_merges_ops(const dtgpu_merges *m, size_t i, uint32_t *out, si
 dtgpu_status dtgpu_merges_text(const dtgpu_merges *m, size_t i, uint8_t *out, size_t cap, size_t *out_len) {
     if (out_len) *out_len = 0;
     if (!m || i >= m->n) return DTGPU_ERR_ARG;
-    if (m->status[i]) return dtgpu_status(m->status[i]);
-    if (!m->n_front[i]) return DTGPU_OK;   // the merged version is ROOT: the empty text
+    if (m->fronts.status[i]) return dtgpu_status(m->fronts.status[i]);
+    if (!m->fronts.n_front[i]) return DTGPU_OK;   // the merged version is ROOT: the empty text
     if (hipSetDevice(m->device) != hipSuccess) return DTGPU_ERR_HIP;
     return dtgpu_batch_text(m->batch.get(), i, out, cap, out_len);
 }

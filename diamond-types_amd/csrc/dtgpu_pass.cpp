@@ -301,7 +301,6 @@ dtgpu_status dtgpu_batch_encode(dtgpu_batch *B, uint32_t flags, float *kernel_ms
     if (flags & ~uint32_t(DTGPU_ENCODE_FULL)) return DTGPU_ERR_ARG;
     if (hipSetDevice(B->device) != hipSuccess) return DTGPU_ERR_HIP;
     hipStream_t s = B->stream;
-#define CK(x) do { if (DTGPU_HIP_FAILED(x)) return DTGPU_ERR_HIP; } while (0)
     if (B->e_desc.empty() && B->n) {   // layout once per batch
         const dtgpu_decoded &Dd = *B->dec;
         B->e_desc.assign(B->n, EncDesc{});
@@ -331,11 +330,11 @@ dtgpu_status dtgpu_batch_encode(dtgpu_batch *B, uint32_t flags, float *kernel_ms
             max_agents = std::max(max_agents, r.n_agents);
             max_text = std::max(max_text, r.n_content);
         }
-        CK(B->e_docs.upload(B->e_desc, s));
-        CK(B->e_dres.alloc(B->n));
-        CK(B->e_w.alloc(std::max<uint64_t>(w, 1)));
-        CK(B->e_b.alloc(std::max<uint64_t>(b, 1)));
-        CK(B->e_out.alloc(std::max<uint64_t>(o, 1)));
+        DTGPU_CK(B->e_docs.upload(B->e_desc, s));
+        DTGPU_CK(B->e_dres.alloc(B->n));
+        DTGPU_CK(B->e_w.alloc(std::max<uint64_t>(w, 1)));
+        DTGPU_CK(B->e_b.alloc(std::max<uint64_t>(b, 1)));
+        DTGPU_CK(B->e_out.alloc(std::max<uint64_t>(o, 1)));
         EncParams &q = B->enc;
         q.in = Dd.in.p; q.content = Dd.content.p;
         q.aruns = Dd.aruns.p; q.ent = Dd.ent.p; q.poff = Dd.poff.p; q.par = Dd.par.p; q.cbyte = Dd.cbyte.p;
@@ -366,16 +365,15 @@ dtgpu_status dtgpu_batch_encode(dtgpu_batch *B, uint32_t flags, float *kernel_ms
         if (B->n_gpu_planned && launch_plan(qq, s) != OK) return DTGPU_ERR_HIP;
     }
     B->enc.flags = flags;
-    CK(hipMemsetAsync(B->e_dres.p, 0, std::max<size_t>(B->n, 1) * sizeof(EncResult), s));
-    CK(hipEventRecord(B->ev0, s));
+    DTGPU_CK(hipMemsetAsync(B->e_dres.p, 0, std::max<size_t>(B->n, 1) * sizeof(EncResult), s));
+    DTGPU_CK(hipEventRecord(B->ev0, s));
     if (launch_encode(B->enc, s)) return DTGPU_ERR_HIP;
-    CK(hipEventRecord(B->ev1, s));
+    DTGPU_CK(hipEventRecord(B->ev1, s));
     B->e_res.resize(B->n);
-    CK(hipMemcpyAsync(B->e_res.data(), B->e_dres.p, B->n * sizeof(EncResult), hipMemcpyDeviceToHost, s));
-    CK(hipStreamSynchronize(s));
+    DTGPU_CK(hipMemcpyAsync(B->e_res.data(), B->e_dres.p, B->n * sizeof(EncResult), hipMemcpyDeviceToHost, s));
+    DTGPU_CK(hipStreamSynchronize(s));
     float ms = 0;
-    CK(hipEventElapsedTime(&ms, B->ev0, B->ev1));
-#undef CK
+    DTGPU_CK(hipEventElapsedTime(&ms, B->ev0, B->ev1));
     if (kernel_ms) *kernel_ms = ms;
     return DTGPU_OK;
 }

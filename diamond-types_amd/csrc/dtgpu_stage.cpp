@@ -9,8 +9,6 @@
 #include "dt_batch.hpp"
 #include "dt_merge.hpp"
 
-#define CK(x) do { if (DTGPU_HIP_FAILED(x)) return DTGPU_ERR_HIP; } while (0)
-
 namespace dtgpu {
 
 Settings settings_for(const dtgpu_batch_opts *o) {
@@ -121,7 +119,7 @@ bool over_block_limit(uint64_t n_ins) { return n_ins / 32 + 2 > std::min<uint64_
 
 // A new batch of n documents on B.device: the device's CU count, the per-document vectors.
 dtgpu_status begin_batch(dtgpu_batch &B, size_t n) {
-    CK(hipSetDevice(B.device));
+    DTGPU_CK(hipSetDevice(B.device));
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, B.device) == hipSuccess && prop.multiProcessorCount > 0)
         B.n_cu = prop.multiProcessorCount;
@@ -197,11 +195,11 @@ dtgpu_status size_plans(dtgpu_batch &B, const std::vector<PlanDesc> &pdesc, uint
                         uint32_t max_agents, std::vector<PlanResult> &pres, std::vector<uint32_t> *wres) {
     const size_t n = B.n;
     hipStream_t s = B.stream;
-    CK(B.p_order.alloc(std::max<uint64_t>(erec_words / EREC_WORDS, 1)));
-    CK(B.p_walk.alloc(2 * std::max<size_t>(n, 1)));
-    CK(B.p_docs.upload(pdesc, s));
-    CK(B.p_results.alloc(n));
-    CK(hipMemsetAsync(B.p_results.p, 0, std::max<size_t>(n, 1) * sizeof(PlanResult), s));
+    DTGPU_CK(B.p_order.alloc(std::max<uint64_t>(erec_words / EREC_WORDS, 1)));
+    DTGPU_CK(B.p_walk.alloc(2 * std::max<size_t>(n, 1)));
+    DTGPU_CK(B.p_docs.upload(pdesc, s));
+    DTGPU_CK(B.p_results.alloc(n));
+    DTGPU_CK(hipMemsetAsync(B.p_results.p, 0, std::max<size_t>(n, 1) * sizeof(PlanResult), s));
     PlanParams &q = B.plan;
     q.par = B.p_par.p; q.pent = B.p_pent.p; q.pch = B.p_pch.p; q.pcnt = B.p_pcnt.p;
     q.child = B.p_child.p; q.opc = B.p_opc.p;
@@ -217,12 +215,12 @@ dtgpu_status size_plans(dtgpu_batch &B, const std::vector<PlanDesc> &pdesc, uint
     if (launch_plan(q, s) != OK) { DTGPU_HIP_FAILED(hipErrorLaunchFailure); return DTGPU_ERR_HIP; }
     q.count_only = 0;
     pres.resize(n);
-    CK(hipMemcpyAsync(pres.data(), B.p_results.p, std::max<size_t>(n, 1) * sizeof(PlanResult), hipMemcpyDeviceToHost, s));
+    DTGPU_CK(hipMemcpyAsync(pres.data(), B.p_results.p, std::max<size_t>(n, 1) * sizeof(PlanResult), hipMemcpyDeviceToHost, s));
     if (wres) {
         wres->resize(2 * n);
-        CK(hipMemcpyAsync(wres->data(), q.walk, 2 * n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        DTGPU_CK(hipMemcpyAsync(wres->data(), q.walk, 2 * n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     }
-    CK(hipStreamSynchronize(s));
+    DTGPU_CK(hipStreamSynchronize(s));
     return DTGPU_OK;
 }
 
@@ -300,16 +298,16 @@ dtgpu_status set_tier_params(dtgpu_batch &B, const uint32_t *cbyte, const uint8_
     for (int t = 0; t < kLdsTiers; t++) B.tier[t].n_cu = uint32_t(B.n_cu);
     B.large.n_cu = uint32_t(B.n_cu);
     B.debug = base.debug;
-    if (!B.ev_fork) CK(hipEventCreateWithFlags(&B.ev_fork, hipEventDisableTiming));
-    if (!B.ev_splan) CK(hipEventCreateWithFlags(&B.ev_splan, hipEventDisableTiming));
+    if (!B.ev_fork) DTGPU_CK(hipEventCreateWithFlags(&B.ev_fork, hipEventDisableTiming));
+    if (!B.ev_splan) DTGPU_CK(hipEventCreateWithFlags(&B.ev_splan, hipEventDisableTiming));
     // the late pipeline's two streams at the lowest priority: whenever workgroups of both pipelines
     // wait for a slot, the first round's go first (its whole documents are the pass's critical path)
     int prio_least = 0, prio_greatest = 0;
-    if (B.late_pipe) CK(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
+    if (B.late_pipe) DTGPU_CK(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
     for (int k = 0; k < kSideStreams; k++) {
-        if (!B.side[k] && B.late_pipe && k < 2) CK(hipStreamCreateWithPriority(&B.side[k], hipStreamNonBlocking, prio_least));
-        if (!B.side[k]) CK(hipStreamCreateWithFlags(&B.side[k], hipStreamNonBlocking));
-        if (!B.ev_join[k]) CK(hipEventCreateWithFlags(&B.ev_join[k], hipEventDisableTiming));
+        if (!B.side[k] && B.late_pipe && k < 2) DTGPU_CK(hipStreamCreateWithPriority(&B.side[k], hipStreamNonBlocking, prio_least));
+        if (!B.side[k]) DTGPU_CK(hipStreamCreateWithFlags(&B.side[k], hipStreamNonBlocking));
+        if (!B.ev_join[k]) DTGPU_CK(hipEventCreateWithFlags(&B.ev_join[k], hipEventDisableTiming));
     }
     return DTGPU_OK;
 }
@@ -483,21 +481,21 @@ void mark_critical(dtgpu_batch &B) {
 // the segments' source-list arena and combine step.
 dtgpu_status alloc_arenas(dtgpu_batch &B, const Totals &T, const uint32_t *cbyte, const uint8_t *content) {
     hipStream_t s = B.stream;
-    CK(B.d_lists.upload(tier_lists(B), s));
-    CK(B.d_pos.alloc(T.pc));
-    CK(B.d_ao.alloc(T.pc));
-    CK(B.d_items.alloc(T.blk * 64));
-    CK(B.d_m2.alloc(2 * T.blk));
-    CK(B.d_out.alloc(T.out));
-    CK(B.d_gidx.alloc(T.gidx));
-    CK(B.d_fb.alloc(n_lds_docs(B) + 1));
-    CK(B.d_counter.alloc(2));
-    CK(B.d_results.alloc(B.docs.size()));
-    CK(hipMemsetAsync(B.d_results.p, 0, std::max<size_t>(B.docs.size(), 1) * sizeof(DocResult), s));
-    CK(B.d_src.alloc(std::max<uint64_t>(T.src, 1)));
+    DTGPU_CK(B.d_lists.upload(tier_lists(B), s));
+    DTGPU_CK(B.d_pos.alloc(T.pc));
+    DTGPU_CK(B.d_ao.alloc(T.pc));
+    DTGPU_CK(B.d_items.alloc(T.blk * 64));
+    DTGPU_CK(B.d_m2.alloc(2 * T.blk));
+    DTGPU_CK(B.d_out.alloc(T.out));
+    DTGPU_CK(B.d_gidx.alloc(T.gidx));
+    DTGPU_CK(B.d_fb.alloc(n_lds_docs(B) + 1));
+    DTGPU_CK(B.d_counter.alloc(2));
+    DTGPU_CK(B.d_results.alloc(B.docs.size()));
+    DTGPU_CK(hipMemsetAsync(B.d_results.p, 0, std::max<size_t>(B.docs.size(), 1) * sizeof(DocResult), s));
+    DTGPU_CK(B.d_src.alloc(std::max<uint64_t>(T.src, 1)));
     if (!B.seg_groups.empty()) {
-        CK(B.d_groups.upload(B.seg_groups, s));
-        CK(B.d_segdocs.upload(B.seg_docs, s));
+        DTGPU_CK(B.d_groups.upload(B.seg_groups, s));
+        DTGPU_CK(B.d_segdocs.upload(B.seg_docs, s));
     }
     CombineParams &c = B.comb;
     c.groups = B.d_groups.p; c.seg_docs = B.d_segdocs.p; c.n_groups = uint32_t(B.seg_groups.size());
@@ -596,8 +594,8 @@ dtgpu_status stage(std::vector<Prepared> &prep, const dtgpu_batch_opts *opts, dt
     B->device = opts ? opts->device : 0;
     const size_t n = prep.size();
     if (begin_batch(*B, n) != DTGPU_OK) return DTGPU_ERR_HIP;
-    CK(hipStreamCreateWithFlags(&B->stream, hipStreamNonBlocking));
-    CK(hipEventCreate(&B->ev0)); CK(hipEventCreate(&B->ev_mid)); CK(hipEventCreate(&B->ev1)); CK(hipEventCreate(&B->ev_prep));
+    DTGPU_CK(hipStreamCreateWithFlags(&B->stream, hipStreamNonBlocking));
+    DTGPU_CK(hipEventCreate(&B->ev0)); DTGPU_CK(hipEventCreate(&B->ev_mid)); DTGPU_CK(hipEventCreate(&B->ev1)); DTGPU_CK(hipEventCreate(&B->ev_prep));
     hipStream_t s = B->stream;
     const int threads = threads_for(opts, n);
     const bool force_host = xf || B->cfg.host_plan;
@@ -651,11 +649,11 @@ dtgpu_status stage(std::vector<Prepared> &prep, const dtgpu_batch_opts *opts, dt
             lds_entries = std::max<uint32_t>(lds_entries, uint32_t(ne));
             max_agents = std::max<uint32_t>(max_agents, pi.n_chains);
         }
-        CK(B->p_par.upload(par, s)); CK(B->p_pent.upload(pent, s)); CK(B->p_child.upload(child, s));
-        CK(B->p_pch.upload(pch, s)); CK(B->p_pcnt.upload(pcnt, s));
-        CK(B->p_opc.upload(opc, s)); CK(B->d_aruns.upload(aruns, s)); CK(B->p_tip.upload(tip, s));
-        CK(B->p_erec.upload(erec, s)); CK(B->p_doff.upload(doff, s)); CK(B->p_dense.upload(dense, s));
-        CK(B->p_base.upload(base_rows, s));
+        DTGPU_CK(B->p_par.upload(par, s)); DTGPU_CK(B->p_pent.upload(pent, s)); DTGPU_CK(B->p_child.upload(child, s));
+        DTGPU_CK(B->p_pch.upload(pch, s)); DTGPU_CK(B->p_pcnt.upload(pcnt, s));
+        DTGPU_CK(B->p_opc.upload(opc, s)); DTGPU_CK(B->d_aruns.upload(aruns, s)); DTGPU_CK(B->p_tip.upload(tip, s));
+        DTGPU_CK(B->p_erec.upload(erec, s)); DTGPU_CK(B->p_doff.upload(doff, s)); DTGPU_CK(B->p_dense.upload(dense, s));
+        DTGPU_CK(B->p_base.upload(base_rows, s));
         erec_words = erec.size();
     }
     B->plan.prow = B->p_base.p;
@@ -733,11 +731,11 @@ dtgpu_status stage(std::vector<Prepared> &prep, const dtgpu_batch_opts *opts, dt
         if (!extra.empty()) {
             std::vector<uint32_t> all(B->d_aruns.n);
             if (B->d_aruns.n)
-                CK(hipMemcpyAsync(all.data(), B->d_aruns.p, all.size() * 4, hipMemcpyDeviceToHost, s));
-            CK(hipStreamSynchronize(s));
+                DTGPU_CK(hipMemcpyAsync(all.data(), B->d_aruns.p, all.size() * 4, hipMemcpyDeviceToHost, s));
+            DTGPU_CK(hipStreamSynchronize(s));
             append(all, extra);
             DevBuf<uint32_t> fresh;
-            CK(fresh.upload(all, s));
+            DTGPU_CK(fresh.upload(all, s));
             std::swap(B->d_aruns.p, fresh.p);
             std::swap(B->d_aruns.n, fresh.n);
             B->plan.aruns = B->d_aruns.p;
@@ -756,16 +754,16 @@ dtgpu_status stage(std::vector<Prepared> &prep, const dtgpu_batch_opts *opts, dt
     }
     hcmds.resize(T.cmd);
     htlist.resize(T.tlist);
-    CK(B->d_cmds.upload(hcmds, s));
-    CK(B->d_tlist.upload(htlist, s));
-    CK(B->p_docs.upload(pdesc, s));
+    DTGPU_CK(B->d_cmds.upload(hcmds, s));
+    DTGPU_CK(B->d_tlist.upload(htlist, s));
+    DTGPU_CK(B->p_docs.upload(pdesc, s));
     B->plan.docs = B->p_docs.p;
     B->plan.cmds = B->d_cmds.p;
     B->plan.tlist = B->d_tlist.p;
-    CK(B->d_cbyte.upload(cbyte, s));
-    CK(B->d_content.upload(content, s));
+    DTGPU_CK(B->d_cbyte.upload(cbyte, s));
+    DTGPU_CK(B->d_content.upload(content, s));
     mark_critical(*B);
-    CK(B->d_docs.upload(B->docs, s));
+    DTGPU_CK(B->d_docs.upload(B->docs, s));
     if (alloc_arenas(*B, T, B->d_cbyte.p, B->d_content.p) != DTGPU_OK) return DTGPU_ERR_HIP;
     {   // linear documents: their op runs as the decoder's quads (lv, len, pos, kind | fwd << 1)
         std::vector<FFIn> ffin;
@@ -776,15 +774,15 @@ dtgpu_status stage(std::vector<Prepared> &prep, const dtgpu_batch_opts *opts, dt
             for (const OpRun &r : prep[i].log.ops)
                 quads.insert(quads.end(), {uint32_t(r.lv), uint32_t(r.len), uint32_t(r.pos), uint32_t(r.kind) | (uint32_t(r.fwd) << 1)});
         }
-        CK(B->f_ops.upload(quads, s));
-        CK(stage_ff(*B, ffin, B->f_ops.p, B->d_cbyte.p, B->d_content.p, s));
+        DTGPU_CK(B->f_ops.upload(quads, s));
+        DTGPU_CK(stage_ff(*B, ffin, B->f_ops.p, B->d_cbyte.p, B->d_content.p, s));
     }
     if (xf) {
-        CK(B->d_mup.alloc(T.blk));
-        CK(B->d_tup.alloc(T.blk + 2 * n));
-        CK(B->d_xf.alloc(T.lv));
+        DTGPU_CK(B->d_mup.alloc(T.blk));
+        DTGPU_CK(B->d_tup.alloc(T.blk + 2 * n));
+        DTGPU_CK(B->d_xf.alloc(T.lv));
     }
-    CK(hipStreamSynchronize(s));
+    DTGPU_CK(hipStreamSynchronize(s));
     B->xf_mode = xf;
     if (set_tier_params(*B, B->d_cbyte.p, B->d_content.p) != DTGPU_OK) return DTGPU_ERR_HIP;
     *out = B.release();
@@ -809,15 +807,15 @@ dtgpu_status stage_device(dtgpu_decoded *dec, const dtgpu_batch_opts *opts, dtgp
     if (begin_batch(*B, n) != DTGPU_OK) return DTGPU_ERR_HIP;
     B->stream = Dd.stream;   // one stream for decode, prep, plan and replay
     Dd.stream = nullptr;     // owned by the batch from here on
-    CK(hipEventCreate(&B->ev0)); CK(hipEventCreate(&B->ev_mid)); CK(hipEventCreate(&B->ev1));
-    CK(hipEventCreate(&B->ev_dec)); CK(hipEventCreate(&B->ev_prep));
-    CK(hipEventCreateWithFlags(&B->ev_w0, hipEventDisableTiming));
-    CK(hipEventCreateWithFlags(&B->ev_w1, hipEventDisableTiming));
+    DTGPU_CK(hipEventCreate(&B->ev0)); DTGPU_CK(hipEventCreate(&B->ev_mid)); DTGPU_CK(hipEventCreate(&B->ev1));
+    DTGPU_CK(hipEventCreate(&B->ev_dec)); DTGPU_CK(hipEventCreate(&B->ev_prep));
+    DTGPU_CK(hipEventCreateWithFlags(&B->ev_w0, hipEventDisableTiming));
+    DTGPU_CK(hipEventCreateWithFlags(&B->ev_w1, hipEventDisableTiming));
     hipStream_t s = B->stream;
     if (!Dd.merged) {
         if (launch_decode(Dd.P, s)) return DTGPU_ERR_HIP;
-        CK(hipMemcpyAsync(Dd.res.data(), Dd.d_res.p, n * sizeof(DecodeResult), hipMemcpyDeviceToHost, s));
-        CK(hipStreamSynchronize(s));
+        DTGPU_CK(hipMemcpyAsync(Dd.res.data(), Dd.d_res.p, n * sizeof(DecodeResult), hipMemcpyDeviceToHost, s));
+        DTGPU_CK(hipStreamSynchronize(s));
     }
     stage_prof("stage: decode pass");
 
@@ -857,14 +855,14 @@ dtgpu_status stage_device(dtgpu_decoded *dec, const dtgpu_batch_opts *opts, dtgp
         q.o_scr = o_scr; o_scr += prep_scratch_words(r.n_parents, r.n_entries);
         max_e = std::max<uint32_t>(max_e, r.n_entries);
     }
-    CK(B->p_par.alloc(o_par)); CK(B->p_pent.alloc(o_par)); CK(B->p_pch.alloc(o_par)); CK(B->p_pcnt.alloc(o_par));
-    CK(B->p_child.alloc(o_par)); CK(B->p_opc.alloc(o_op)); CK(B->d_aruns.alloc(4 * o_arun));
-    CK(B->p_tip.alloc(2 * o_tip)); CK(B->p_erec.alloc(o_erec)); CK(B->p_doff.alloc(o_doff));
-    CK(B->p_dense.alloc(o_dense)); CK(B->pr_rows.alloc(o_rows)); CK(B->pr_scr.alloc(o_scr));
+    DTGPU_CK(B->p_par.alloc(o_par)); DTGPU_CK(B->p_pent.alloc(o_par)); DTGPU_CK(B->p_pch.alloc(o_par)); DTGPU_CK(B->p_pcnt.alloc(o_par));
+    DTGPU_CK(B->p_child.alloc(o_par)); DTGPU_CK(B->p_opc.alloc(o_op)); DTGPU_CK(B->d_aruns.alloc(4 * o_arun));
+    DTGPU_CK(B->p_tip.alloc(2 * o_tip)); DTGPU_CK(B->p_erec.alloc(o_erec)); DTGPU_CK(B->p_doff.alloc(o_doff));
+    DTGPU_CK(B->p_dense.alloc(o_dense)); DTGPU_CK(B->pr_rows.alloc(o_rows)); DTGPU_CK(B->pr_scr.alloc(o_scr));
     // prep stores each entry's parent vector at the chains that exist by then; the words past
     // them stay zero from here on (every pass writes the same words)
-    CK(hipMemsetAsync(B->pr_rows.p, 0, std::max<uint64_t>(o_rows, 1) * sizeof(uint32_t), s));
-    CK(B->pr_docs.upload(pd, s)); CK(B->pr_res.alloc(n));
+    DTGPU_CK(hipMemsetAsync(B->pr_rows.p, 0, std::max<uint64_t>(o_rows, 1) * sizeof(uint32_t), s));
+    DTGPU_CK(B->pr_docs.upload(pd, s)); DTGPU_CK(B->pr_res.alloc(n));
     PrepParams &pp = B->prep;
     pp.in = Dd.in.p;
     pp.d_ops = Dd.ops.p; pp.d_aruns = Dd.aruns.p; pp.d_ent = Dd.ent.p; pp.d_poff = Dd.poff.p; pp.d_par = Dd.par.p;
@@ -873,7 +871,7 @@ dtgpu_status stage_device(dtgpu_decoded *dec, const dtgpu_batch_opts *opts, dtgp
     pp.aruns = B->d_aruns.p; pp.tip = B->p_tip.p; pp.erec = B->p_erec.p; pp.doff = B->p_doff.p; pp.dense = B->p_dense.p;
     pp.rows = B->pr_rows.p; pp.scr = B->pr_scr.p; pp.opc = B->p_opc.p;
     if (B->cfg.prep_chains) {
-        CK(B->pr_chain.alloc(std::max<size_t>(n, 1)));
+        DTGPU_CK(B->pr_chain.alloc(std::max<size_t>(n, 1)));
         pp.chain_flag = B->pr_chain.p;
     }
     pp.docs = B->pr_docs.p; pp.results = B->pr_res.p; pp.n_docs = uint32_t(n); pp.max_entries = max_e;
@@ -881,8 +879,8 @@ dtgpu_status stage_device(dtgpu_decoded *dec, const dtgpu_batch_opts *opts, dtgp
     pp.check = B->cfg.prep_check ? 1u : 0u;
     if (launch_prep(pp, s)) return DTGPU_ERR_HIP;
     std::vector<PrepResult> prr(n);
-    CK(hipMemcpyAsync(prr.data(), B->pr_res.p, n * sizeof(PrepResult), hipMemcpyDeviceToHost, s));
-    CK(hipStreamSynchronize(s));
+    DTGPU_CK(hipMemcpyAsync(prr.data(), B->pr_res.p, n * sizeof(PrepResult), hipMemcpyDeviceToHost, s));
+    DTGPU_CK(hipStreamSynchronize(s));
     stage_prof("stage: prep layout + pass");
 
     // ---- planner sizing pass ----------------------------------------------------------------------
@@ -910,7 +908,7 @@ dtgpu_status stage_device(dtgpu_decoded *dec, const dtgpu_batch_opts *opts, dtgp
         lds_entries = std::max<uint32_t>(lds_entries, r.ne);
         max_agents = std::max<uint32_t>(max_agents, prr[i].n_chains);
     }
-    CK(B->p_base.alloc(base_total));
+    DTGPU_CK(B->p_base.alloc(base_total));
     PlanParams &q = B->plan;
     q.prow = B->pr_rows.p;
     q.coff = B->pr_scr.p;
@@ -1000,8 +998,8 @@ dtgpu_status stage_device(dtgpu_decoded *dec, const dtgpu_batch_opts *opts, dtgp
             DevBuf<SegGroup> dg;
             DevBuf<SegPlan> dp;
             DevBuf<uint32_t> dd, dscr, dout;
-            CK(dg.upload(sg, s)); CK(dp.upload(sp, s)); CK(dd.upload(sdocs, s));
-            CK(dscr.alloc(std::max<uint64_t>(sscr, 1))); CK(dout.alloc(sized.size()));
+            DTGPU_CK(dg.upload(sg, s)); DTGPU_CK(dp.upload(sp, s)); DTGPU_CK(dd.upload(sdocs, s));
+            DTGPU_CK(dscr.alloc(std::max<uint64_t>(sscr, 1))); DTGPU_CK(dout.alloc(sized.size()));
             CutParams c{};
             c.d_ops = Dd.ops.p; c.d_ent = Dd.ent.p; c.d_poff = Dd.poff.p; c.d_par = Dd.par.p;
             c.pdocs = B->pr_docs.p;
@@ -1011,8 +1009,8 @@ dtgpu_status stage_device(dtgpu_decoded *dec, const dtgpu_batch_opts *opts, dtgp
             c.max_ne = smax_ne;
             c.sized = dout.p;
             if (launch_cut(c, s)) return DTGPU_ERR_HIP;
-            CK(hipMemcpyAsync(sized.data(), dout.p, sized.size() * 4, hipMemcpyDeviceToHost, s));
-            CK(hipStreamSynchronize(s));
+            DTGPU_CK(hipMemcpyAsync(sized.data(), dout.p, sized.size() * 4, hipMemcpyDeviceToHost, s));
+            DTGPU_CK(hipStreamSynchronize(s));
         }
         uint64_t scr = 0;
         for (size_t g = 0; g < sg.size(); g++) {
@@ -1026,7 +1024,7 @@ dtgpu_status stage_device(dtgpu_decoded *dec, const dtgpu_batch_opts *opts, dtgp
             scr += (cut_scratch_words(Dd.res[i].n_entries) + 1) & ~1ull;
             B->cut.max_ne = std::max<uint32_t>(B->cut.max_ne, Dd.res[i].n_entries);
         }
-        CK(B->d_cutscr.alloc(std::max<uint64_t>(scr, 1)));
+        DTGPU_CK(B->d_cutscr.alloc(std::max<uint64_t>(scr, 1)));
     }
     stage_prof("stage: layout + cut plans");
     // every later pass: parent-vector rows as wide as the document's chains (staging counted
@@ -1041,11 +1039,11 @@ dtgpu_status stage_device(dtgpu_decoded *dec, const dtgpu_batch_opts *opts, dtgp
         widest = std::max(widest, rs);
     }
     B->prep.chain_w = widest;   // the chain decomposition's LDS ring rows, as wide as needed
-    CK(B->pr_docs.upload(pd, s));
+    DTGPU_CK(B->pr_docs.upload(pd, s));
     B->prep.docs = B->pr_docs.p;
-    CK(B->d_cmds.alloc(T.cmd));
-    CK(B->d_tlist.alloc(T.tlist));
-    CK(B->p_docs.upload(pdesc, s));
+    DTGPU_CK(B->d_cmds.alloc(T.cmd));
+    DTGPU_CK(B->d_tlist.alloc(T.tlist));
+    DTGPU_CK(B->p_docs.upload(pdesc, s));
     B->plan.docs = B->p_docs.p;
     B->plan.cmds = B->d_cmds.p;
     B->plan.tlist = B->d_tlist.p;
@@ -1054,18 +1052,18 @@ dtgpu_status stage_device(dtgpu_decoded *dec, const dtgpu_batch_opts *opts, dtgp
         mark_critical(*B);
         std::vector<DocDesc> up = B->docs;
         for (uint32_t d : B->seg_docs) { up[d].seg_lo = 0xFFFFFFFFu; up[d].seg_hi = 0; }
-        CK(B->d_docs.upload(up, s));
+        DTGPU_CK(B->d_docs.upload(up, s));
     }
     if (alloc_arenas(*B, T, Dd.cbyte.p, Dd.content.p) != DTGPU_OK) return DTGPU_ERR_HIP;
     {   // linear documents: the fast-forward layout over the decoder's op runs, in place
         std::vector<FFIn> ffin;
         for (size_t i = 0; i < n; i++)
             if (B->ff_doc[i]) ffin.push_back(FFIn{Dd.desc[i].op_off, Dd.res[i].n_ops, uint32_t(i)});
-        CK(stage_ff(*B, ffin, Dd.ops.p, Dd.cbyte.p, Dd.content.p, s));
+        DTGPU_CK(stage_ff(*B, ffin, Dd.ops.p, Dd.cbyte.p, Dd.content.p, s));
     }
     if (!B->seg_groups.empty()) {
-        CK(B->d_plans.upload(B->seg_plans, s));
-        CK(B->d_caps.upload(B->seg_caps, s));
+        DTGPU_CK(B->d_plans.upload(B->seg_plans, s));
+        DTGPU_CK(B->d_caps.upload(B->seg_caps, s));
         CutParams &c = B->cut;
         c.d_ops = Dd.ops.p; c.d_ent = Dd.ent.p; c.d_poff = Dd.poff.p; c.d_par = Dd.par.p;
         c.pdocs = B->pr_docs.p;
@@ -1077,15 +1075,15 @@ dtgpu_status stage_device(dtgpu_decoded *dec, const dtgpu_batch_opts *opts, dtgp
         c.scr = B->d_cutscr.p;
         c.pent = B->p_pent.p;
         c.n_groups = uint32_t(B->seg_groups.size());
-        if (!B->ev_cut) CK(hipEventCreateWithFlags(&B->ev_cut, hipEventDisableTiming));
+        if (!B->ev_cut) DTGPU_CK(hipEventCreateWithFlags(&B->ev_cut, hipEventDisableTiming));
     }
     if (xf) {   // the transformed-ops replay's arenas, as stage() allocates them for its xf batches
-        CK(B->d_mup.alloc(T.blk));
-        CK(B->d_tup.alloc(T.blk + 2 * n));
-        CK(B->d_xf.alloc(T.lv));
+        DTGPU_CK(B->d_mup.alloc(T.blk));
+        DTGPU_CK(B->d_tup.alloc(T.blk + 2 * n));
+        DTGPU_CK(B->d_xf.alloc(T.lv));
         B->xf_mode = true;
     }
-    CK(hipStreamSynchronize(s));
+    DTGPU_CK(hipStreamSynchronize(s));
     stage_prof("stage: arenas + uploads");
     if (set_tier_params(*B, Dd.cbyte.p, Dd.content.p) != DTGPU_OK) return DTGPU_ERR_HIP;
     B->wstream = B->side[kSideStreams - 1];   // the smallest side tier's stream (see wstream)
@@ -1111,13 +1109,13 @@ dtgpu_status stage_device(dtgpu_decoded *dec, const dtgpu_batch_opts *opts, dtgp
             for (size_t i = 0; i < n; i++)
                 if (!big[i] && !B->ff_doc[i]) lst.push_back(uint32_t(i));
             if (lst.size() > nb) {
-                CK(B->d_split.upload(lst, s));
-                CK(hipStreamSynchronize(s));
+                DTGPU_CK(B->d_split.upload(lst, s));
+                DTGPU_CK(hipStreamSynchronize(s));
                 B->split = true;
                 B->split_tier = tb;
-                if (!B->ws_side) CK(hipStreamCreateWithFlags(&B->ws_side, hipStreamNonBlocking));
-                if (!B->ev_sw0) CK(hipEventCreateWithFlags(&B->ev_sw0, hipEventDisableTiming));
-                if (!B->ev_sw1) CK(hipEventCreateWithFlags(&B->ev_sw1, hipEventDisableTiming));
+                if (!B->ws_side) DTGPU_CK(hipStreamCreateWithFlags(&B->ws_side, hipStreamNonBlocking));
+                if (!B->ev_sw0) DTGPU_CK(hipEventCreateWithFlags(&B->ev_sw0, hipEventDisableTiming));
+                if (!B->ev_sw1) DTGPU_CK(hipEventCreateWithFlags(&B->ev_sw1, hipEventDisableTiming));
                 B->n_big = uint32_t(nb);
                 B->n_rest = uint32_t(lst.size() - nb);
             }
@@ -1133,12 +1131,12 @@ dtgpu_status stage_device(dtgpu_decoded *dec, const dtgpu_batch_opts *opts, dtgp
         B->n_first = uint32_t(lst.size());
         B->n_late = uint32_t(late.size());
         append(lst, late);
-        CK(B->d_late.upload(lst, s));
-        CK(hipStreamSynchronize(s));
-        if (!B->ev_sw0) CK(hipEventCreateWithFlags(&B->ev_sw0, hipEventDisableTiming));
-        if (!B->ev_sw1) CK(hipEventCreateWithFlags(&B->ev_sw1, hipEventDisableTiming));
-        if (!B->ev_lprep) CK(hipEventCreateWithFlags(&B->ev_lprep, hipEventDisableTiming));
-        if (!B->ev_lgo) CK(hipEventCreateWithFlags(&B->ev_lgo, hipEventDisableTiming));
+        DTGPU_CK(B->d_late.upload(lst, s));
+        DTGPU_CK(hipStreamSynchronize(s));
+        if (!B->ev_sw0) DTGPU_CK(hipEventCreateWithFlags(&B->ev_sw0, hipEventDisableTiming));
+        if (!B->ev_sw1) DTGPU_CK(hipEventCreateWithFlags(&B->ev_sw1, hipEventDisableTiming));
+        if (!B->ev_lprep) DTGPU_CK(hipEventCreateWithFlags(&B->ev_lprep, hipEventDisableTiming));
+        if (!B->ev_lgo) DTGPU_CK(hipEventCreateWithFlags(&B->ev_lgo, hipEventDisableTiming));
     }
     stage_prof("stage: split setup");
     *out = B.release();

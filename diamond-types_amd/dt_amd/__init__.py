@@ -284,6 +284,39 @@ def _u64s(xs):
     return (ctypes.c_uint64 * max(1, len(xs)))(*xs), len(xs)
 
 
+def _csr(sets, n):
+    """n sets of LVs flattened for the C ABI: (the u64 values, the n + 1 offsets)."""
+    flat, off = [], [0]
+    for v in sets:
+        flat.extend(int(x) for x in v)
+        off.append(len(flat))
+    return _u64s(flat)[0], (ctypes.c_size_t * (n + 1))(*off)
+
+
+def _sized(call, make):
+    """The C ABI's sized read: call(None, 0, byref(n)) asks the length, call(buf, n, byref(n)) fills
+    buf = make(n).  Returns (buf, n)."""
+    n = ctypes.c_size_t()
+    _check(call(None, 0, ctypes.byref(n)))
+    buf = make(n.value)
+    _check(call(buf, n.value, ctypes.byref(n)))
+    return buf, n.value
+
+
+def _sized_bytes(call) -> bytes:
+    """_sized into a byte buffer: the bytes."""
+    buf, n = _sized(call, lambda k: ctypes.create_string_buffer(max(1, k)))
+    return buf.raw[:n]
+
+
+def _frontier_result(fn, handle, i):
+    """(status, frontier) of request i through a *_result call; a reduced frontier has at most 64 LVs."""
+    k = ctypes.c_size_t()
+    buf = (ctypes.c_uint64 * 64)()
+    st = fn(handle, i, buf, 64, ctypes.byref(k))
+    return st, list(buf[:k.value])
+
+
 def _name_bytes(name) -> bytes:
     return bytes(name) if isinstance(name, (bytes, bytearray)) else str(name).encode()
 
@@ -495,11 +528,7 @@ ENCODE_PATCH = EncodeOptions(True, True, False)   # encode_oplog.rs:112-120
 def lz4_compress(data: bytes) -> bytes:
     """lz4_flex::compress_into as the encoder calls it (encode_oplog.rs:320-343): one raw LZ4
     block, no length prefix."""
-    n = ctypes.c_size_t()
-    _check(lib().dtgpu_lz4_compress(data, len(data), None, 0, ctypes.byref(n)))
-    buf = ctypes.create_string_buffer(max(1, n.value))
-    _check(lib().dtgpu_lz4_compress(data, len(data), buf, n.value, ctypes.byref(n)))
-    return buf.raw[:n.value]
+    return _sized_bytes(lambda *a: lib().dtgpu_lz4_compress(data, len(data), *a))
 
 
 class ListOpLog:
@@ -637,11 +666,7 @@ class ListOpLog:
         return [(int(buf[2 * k]), int(buf[2 * k + 1])) for k in range(n)]
 
     def checkout_tip_bytes(self) -> bytes:
-        n = ctypes.c_size_t()
-        _check(lib().dtgpu_checkout_tip(self._h, None, 0, ctypes.byref(n)))
-        buf = ctypes.create_string_buffer(max(1, n.value))
-        _check(lib().dtgpu_checkout_tip(self._h, buf, n.value, ctypes.byref(n)))
-        return buf.raw[:n.value]
+        return _sized_bytes(lambda *a: lib().dtgpu_checkout_tip(self._h, *a))
 
     def checkout_tip(self) -> ListBranch:
         return ListBranch(self.checkout_tip_bytes(), self.local_frontier())
@@ -666,12 +691,9 @@ class ListOpLog:
             frm, merging = [], self.local_frontier()
         pa, na = _u64s(frm or [])
         pb, nb = _u64s(merging or [])
-        k = ctypes.c_size_t()
-        _check(lib().dtgpu_xf_operations_from(self._h, pa, na, pb, nb, None, 0, ctypes.byref(k)))
-        n = k.value
-        buf = (ctypes.c_uint32 * max(2, 2 * n))()
-        _check(lib().dtgpu_xf_operations_from(self._h, pa, na, pb, nb, buf, n, ctypes.byref(k)))
-        return [(buf[2 * i], None if buf[2 * i + 1] == 0xFFFFFFFF else buf[2 * i + 1]) for i in range(k.value)]
+        buf, n = _sized(lambda *a: lib().dtgpu_xf_operations_from(self._h, pa, na, pb, nb, *a),
+                        lambda k: (ctypes.c_uint32 * max(2, 2 * k))())
+        return [(buf[2 * i], None if buf[2 * i + 1] == 0xFFFFFFFF else buf[2 * i + 1]) for i in range(n)]
 
     def iter_xf_operations_from(self, frm, merging):
         """ListOpLog::iter_xf_operations_from (src/list/merge.rs:24-38); see iter_xf_operations."""
@@ -696,11 +718,7 @@ class ListOpLog:
         the checkout at `frm`, run on the GPU."""
         p, nf = _u64s(frm)
         flags = (opts or ENCODE_FULL).flags()
-        n = ctypes.c_size_t()
-        _check(lib().dtgpu_oplog_encode(self._h, p, nf, flags, None, 0, ctypes.byref(n)))
-        buf = ctypes.create_string_buffer(max(1, n.value))
-        _check(lib().dtgpu_oplog_encode(self._h, p, nf, flags, buf, n.value, ctypes.byref(n)))
-        return buf.raw[:n.value]
+        return _sized_bytes(lambda *a: lib().dtgpu_oplog_encode(self._h, p, nf, flags, *a))
 
     def dominators(self, a, b=()):
         """Graph::find_dominators_2 (src/causalgraph/graph/tools.rs:545-578) over this oplog."""
@@ -715,11 +733,7 @@ class ListOpLog:
 
     def checkout_bytes(self, version) -> bytes:
         p, nv = _u64s(version)
-        n = ctypes.c_size_t()
-        _check(lib().dtgpu_checkout(self._h, p, nv, None, 0, ctypes.byref(n)))
-        buf = ctypes.create_string_buffer(max(1, n.value))
-        _check(lib().dtgpu_checkout(self._h, p, nv, buf, n.value, ctypes.byref(n)))
-        return buf.raw[:n.value]
+        return _sized_bytes(lambda *a: lib().dtgpu_checkout(self._h, p, nv, *a))
 
     def history(self, version) -> "ListOpLog":
         """The history of `version` as its own oplog (dtgpu_oplog_history)."""
@@ -897,11 +911,8 @@ class Batch:
 
     def xf_positions(self, i):
         """Per-LV BaseMoved positions of document i (xf batches; None = DeleteAlreadyHappened)."""
-        k = ctypes.c_size_t()
-        _check(lib().dtgpu_batch_xf_positions(self._h, i, None, 0, ctypes.byref(k)))
-        buf = (ctypes.c_uint32 * max(1, k.value))()
-        _check(lib().dtgpu_batch_xf_positions(self._h, i, buf, k.value, ctypes.byref(k)))
-        return [None if x == 0xFFFFFFFF else x for x in buf[:k.value]]
+        buf, n = _sized(lambda *a: lib().dtgpu_batch_xf_positions(self._h, i, *a), lambda k: (ctypes.c_uint32 * max(1, k))())
+        return [None if x == 0xFFFFFFFF else x for x in buf[:n]]
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -931,11 +942,7 @@ class Batch:
         return ms.value
 
     def encoded(self, i) -> bytes:
-        n = ctypes.c_size_t()
-        _check(lib().dtgpu_batch_encoded(self._h, i, None, 0, ctypes.byref(n), None))
-        buf = ctypes.create_string_buffer(max(1, n.value))
-        _check(lib().dtgpu_batch_encoded(self._h, i, buf, n.value, ctypes.byref(n), None))
-        return buf.raw[:n.value]
+        return _sized_bytes(lambda *a: lib().dtgpu_batch_encoded(self._h, i, *a, None))
 
     def encoded_status(self, i) -> int:
         n = ctypes.c_size_t()
@@ -960,11 +967,7 @@ class Batch:
         return [dict(status=r.status, text_len=r.text_len, text_hash=r.text_hash, n_lv=r.n_lv) for r in arr[:self.n]]
 
     def text(self, i) -> bytes:
-        n = ctypes.c_size_t()
-        _check(lib().dtgpu_batch_text(self._h, i, None, 0, ctypes.byref(n)))
-        buf = ctypes.create_string_buffer(max(1, n.value))
-        _check(lib().dtgpu_batch_text(self._h, i, buf, n.value, ctypes.byref(n)))
-        return buf.raw[:n.value]
+        return _sized_bytes(lambda *a: lib().dtgpu_batch_text(self._h, i, *a))
 
     def last_times(self):
         """(plan_ms, replay_ms, prep_ms) of the last run_timed() (prep_ms 0 when host-staged)."""
@@ -1103,10 +1106,7 @@ class DecodeBatch:
 
     def add_result(self, i):
         """(status, the patch's version): decode_and_add's Result for document i of a merged batch."""
-        k = ctypes.c_size_t()
-        buf = (ctypes.c_uint64 * 64)()
-        st = lib().dtgpu_decode_add_result(self._h, i, buf, 64, ctypes.byref(k))
-        return st, list(buf[:k.value])
+        return _frontier_result(lib().dtgpu_decode_add_result, self._h, i)
 
     def history(self, docs, versions):
         """ListOpLog::checkout(&[LV]) up to the replay, batched on the GPU (dtgpu_decode_history):
@@ -1115,13 +1115,8 @@ class DecodeBatch:
         n = len(docs)
         if len(versions) != n:
             raise ValueError("one version per document index")
-        flat, off = [], [0]
-        for v in versions:
-            flat.extend(int(x) for x in v)
-            off.append(len(flat))
         d = (ctypes.c_uint32 * max(n, 1))(*[int(x) for x in docs])
-        pv, _ = _u64s(flat)
-        po = (ctypes.c_size_t * (n + 1))(*off)
+        pv, po = _csr(versions, n)
         ms = ctypes.c_float()
         h = ctypes.c_void_p()
         _check(lib().dtgpu_decode_history(self._h, d, pv, po, n, ctypes.byref(ms), ctypes.byref(h)))
@@ -1132,10 +1127,7 @@ class DecodeBatch:
     def history_result(self, i):
         """(status, the request reduced to a frontier in the base document's LVs) of output i of a
         history batch."""
-        k = ctypes.c_size_t()
-        buf = (ctypes.c_uint64 * 64)()
-        st = lib().dtgpu_decode_history_result(self._h, i, buf, 64, ctypes.byref(k))
-        return st, list(buf[:k.value])
+        return _frontier_result(lib().dtgpu_decode_history_result, self._h, i)
 
     def encode_from(self, docs, versions, opts=None):
         """ListOpLog::encode_from(opts, versions[i]) of document docs[i] for a whole batch, on the GPU
@@ -1144,13 +1136,8 @@ class DecodeBatch:
         n = len(docs)
         if len(versions) != n:
             raise ValueError("one version per document index")
-        flat, off = [], [0]
-        for v in versions:
-            flat.extend(int(x) for x in v)
-            off.append(len(flat))
         d = (ctypes.c_uint32 * max(n, 1))(*[int(x) for x in docs])
-        pv, _ = _u64s(flat)
-        po = (ctypes.c_size_t * (n + 1))(*off)
+        pv, po = _csr(versions, n)
         ms = ctypes.c_float()
         h = ctypes.c_void_p()
         flags = (opts or ENCODE_PATCH).flags()
@@ -1218,16 +1205,8 @@ class DecodeBatch:
         n = len(docs)
         if len(frm) != n or len(merging) != n:
             raise ValueError("one from and one merging version per document index")
-
-        def csr(vs):
-            flat, off = [], [0]
-            for v in vs:
-                flat.extend(int(x) for x in v)
-                off.append(len(flat))
-            return _u64s(flat)[0], (ctypes.c_size_t * (n + 1))(*off)
-
-        pa, oa = csr(frm)
-        pb, ob = csr(merging)
+        pa, oa = _csr(frm, n)
+        pb, ob = _csr(merging, n)
         d = (ctypes.c_uint32 * max(n, 1))(*[int(x) for x in docs])
         ms, h = ctypes.c_float(), ctypes.c_void_p()
         _check(lib().dtgpu_decode_xf_from(self._h, d, pa, oa, pb, ob, n, ctypes.byref(ms), ctypes.byref(h)))
@@ -1272,8 +1251,11 @@ class DecodeBatch:
         return lib().dtgpu_decode_bytes(self._h, 1)
 
 
-class PatchBatch:
-    """The patches of one DecodeBatch.encode_from call (dtgpu_patches), resident on the device."""
+class _ResultBatch:
+    """What one per-request call over a DecodeBatch returned: a device-side handle of n requests,
+    each with a status and a reduced frontier.  A subclass names its C functions (dtgpu_<_C>_result /
+    _profile / _free) and the width of its profile record."""
+    _C, _PROFILE = None, 8
 
     def __init__(self, handle, n, last_ms):
         self._h, self.n, self.last_ms = handle, n, last_ms
@@ -1284,17 +1266,24 @@ class PatchBatch:
     def __del__(self):
         h = getattr(self, "_h", None)
         if h:
-            lib().dtgpu_patches_free(h)
+            getattr(lib(), f"dtgpu_{self._C}_free")(h)
             self._h = None
 
     def _result(self, i):
-        k = ctypes.c_size_t()
-        buf = (ctypes.c_uint64 * 64)()
-        st = lib().dtgpu_patches_result(self._h, i, buf, 64, ctypes.byref(k))
-        return st, list(buf[:k.value])
+        return _frontier_result(getattr(lib(), f"dtgpu_{self._C}_result"), self._h, i)
 
     def status(self, i) -> int:
         return self._result(i)[0]
+
+    def _profile(self, i):
+        out = (ctypes.c_uint32 * self._PROFILE)()
+        _check(getattr(lib(), f"dtgpu_{self._C}_profile")(self._h, i, out))
+        return list(out)
+
+
+class PatchBatch(_ResultBatch):
+    """The patches of one DecodeBatch.encode_from call (dtgpu_patches), resident on the device."""
+    _C, _PROFILE = "patches", 12
 
     def frontier(self, i):
         """Request i reduced to a frontier, in the base document's LVs, ascending."""
@@ -1303,44 +1292,21 @@ class PatchBatch:
     def profile(self, i):
         """dtgpu_patches_profile: [mark form (1 LDS, 2 HBM), mark us, build us, walk steps, then --
         when DTGPU_PATCH_PROF was set at the call -- the build wave's cycles in its seven phases]."""
-        out = (ctypes.c_uint32 * 12)()
-        _check(lib().dtgpu_patches_profile(self._h, i, out))
-        return list(out)
+        return self._profile(i)
 
     def patch(self, i) -> bytes:
         """Request i's `.dt` patch; ParseError carries a non-zero status."""
-        n = ctypes.c_size_t()
-        _check(lib().dtgpu_patches_get(self._h, i, None, 0, ctypes.byref(n)))
-        buf = ctypes.create_string_buffer(max(1, n.value))
-        _check(lib().dtgpu_patches_get(self._h, i, buf, n.value, ctypes.byref(n)))
-        return buf.raw[:n.value]
+        return _sized_bytes(lambda *a: lib().dtgpu_patches_get(self._h, i, *a))
 
 
-class MergeBatch:
+class MergeBatch(_ResultBatch):
     """The merges of one DecodeBatch.xf_operations_from call (dtgpu_merges): per request the merged
     version, the transformed operations and the merged content."""
+    _C = "merges"
 
     def __init__(self, handle, n, last_ms, base, docs):
-        self._h, self.n, self.last_ms, self._base, self._docs = handle, n, last_ms, base, docs
-        self._arrays = {}
-
-    def __len__(self):
-        return self.n
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            lib().dtgpu_merges_free(h)
-            self._h = None
-
-    def _result(self, i):
-        k = ctypes.c_size_t()
-        buf = (ctypes.c_uint64 * 64)()
-        st = lib().dtgpu_merges_result(self._h, i, buf, 64, ctypes.byref(k))
-        return st, list(buf[:k.value])
-
-    def status(self, i) -> int:
-        return self._result(i)[0]
+        super().__init__(handle, n, last_ms)
+        self._base, self._docs, self._arrays = base, docs, {}
 
     def version(self, i):
         """find_dominators_2(from, merging) in the base document's LVs, ascending."""
@@ -1350,11 +1316,7 @@ class MergeBatch:
 
     def xf_operations_lv(self, i):
         """[(lv, pos or None)] in application order: ListOpLog.xf_operations_lv(frm, merging)."""
-        k = ctypes.c_size_t()
-        _check(lib().dtgpu_merges_ops(self._h, i, None, 0, ctypes.byref(k)))
-        n = k.value
-        buf = (ctypes.c_uint32 * max(2, 2 * n))()
-        _check(lib().dtgpu_merges_ops(self._h, i, buf, n, ctypes.byref(k)))
+        buf, n = _sized(lambda *a: lib().dtgpu_merges_ops(self._h, i, *a), lambda k: (ctypes.c_uint32 * max(2, 2 * k))())
         import numpy as np
         a = np.frombuffer(buf, dtype=np.uint32, count=2 * n).reshape(-1, 2).tolist()
         return [(lv, None if x == 0xFFFFFFFF else x) for lv, x in a]
@@ -1371,43 +1333,21 @@ class MergeBatch:
 
     def content_bytes(self, i) -> bytes:
         """The branch's content after the merge: the checkout at version(i)."""
-        n = ctypes.c_size_t()
-        _check(lib().dtgpu_merges_text(self._h, i, None, 0, ctypes.byref(n)))
-        buf = ctypes.create_string_buffer(max(1, n.value))
-        _check(lib().dtgpu_merges_text(self._h, i, buf, n.value, ctypes.byref(n)))
-        return buf.raw[:n.value]
+        return _sized_bytes(lambda *a: lib().dtgpu_merges_text(self._h, i, *a))
 
     def profile(self, i):
         """dtgpu_merges_profile: the batch's us in mark + projection, prep, plan, replay, LV
         translation; then request i's commands, first reported command, reported LVs."""
-        out = (ctypes.c_uint32 * 8)()
-        _check(lib().dtgpu_merges_profile(self._h, i, out))
-        return list(out)
+        return self._profile(i)
 
 
-class IntersectBatch:
+class IntersectBatch(_ResultBatch):
     """The intersections of one DecodeBatch.intersect / sync call (dtgpu_intersect)."""
+    _C = "intersect"
 
     def __init__(self, handle, n, last_ms, names):
-        self._h, self.n, self.last_ms, self._names = handle, n, last_ms, names
-
-    def __len__(self):
-        return self.n
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            lib().dtgpu_intersect_free(h)
-            self._h = None
-
-    def _result(self, i):
-        k = ctypes.c_size_t()
-        buf = (ctypes.c_uint64 * 64)()
-        st = lib().dtgpu_intersect_result(self._h, i, buf, 64, ctypes.byref(k))
-        return st, list(buf[:k.value])
-
-    def status(self, i) -> int:
-        return self._result(i)[0]
+        super().__init__(handle, n, last_ms)
+        self._names = names
 
     def frontier(self, i):
         """The version request i's peer and the document share, in the document's LVs, ascending."""
@@ -1437,9 +1377,7 @@ class IntersectBatch:
     def profile(self, i):
         """dtgpu_intersect_profile: [known pieces, remainder records, re-ordered ranges, count us,
         emit us, mark us, 0, 0]."""
-        out = (ctypes.c_uint32 * 8)()
-        _check(lib().dtgpu_intersect_profile(self._h, i, out))
-        return list(out)
+        return self._profile(i)
 
 
 GQ_KINDS = {"diff": 0, "conflict": 1, "contains": 2, "dominators": 3, "diff_level": 4, "conflict_level": 5}

@@ -1,10 +1,12 @@
 """Device decode_and_add throughput (dtgpu_decode_add): N resident copies of a benchmark file's
 history at half its length, each merged with (a) the patch after that version (catch-up) and
-(b) the whole file (overlap filter).  Prints the merge kernel's ms and documents/s, beside the
-host decode_and_add (dt_host.cpp, one thread) on the same pair.
+(b) the whole file (overlap filter).  Prints the merge kernel's ms and documents/s and the median
+synchronised call time (add_call_s: four calls, the first dropped as warm-up), beside the host
+decode_and_add (dt_host.cpp, one thread) on the same pair.
 
 usage: python tools/addbench.py [name] [n_docs]"""
 import os
+import statistics
 import sys
 import time
 
@@ -25,12 +27,15 @@ def main():
     d = dt_amd.DecodeBatch([part] * n)
     d.run()
     for label, p in (("catch-up", patch), ("overlap", data)):
-        best = None
-        for _ in range(3):
+        best, calls = None, []
+        for _ in range(4):
+            t0 = time.perf_counter()
             m = d.add([p] * n)
+            calls.append(time.perf_counter() - t0)
             assert all(m.add_result(i)[0] == 0 for i in (0, n - 1))
             best = m.last_ms if best is None else min(best, m.last_ms)
             del m
+        call_s = statistics.median(calls[1:])
         k, host = 20, 0.0
         for _ in range(k):
             h = dt_amd.ListOpLog.load_from(part)
@@ -39,7 +44,7 @@ def main():
             host += time.perf_counter() - t0
         host_ms = host / k * 1e3
         print(f"{name} {label}: {n} docs, patch {len(p)} B: device merge {best:.2f} ms "
-              f"({n / best * 1e3:.0f} docs/s); host decode_and_add {host_ms:.3f} ms/doc "
+              f"({n / best * 1e3:.0f} docs/s), add_call_s {call_s:.6f}; host decode_and_add {host_ms:.3f} ms/doc "
               f"({1e3 / host_ms:.0f} docs/s, one thread)", flush=True)
 
 
