@@ -90,6 +90,18 @@ DEV uint32_t c_up(uint32_t c) { return (c >> 24) & 0x7Fu; }
 DEV uint32_t pc_blk(uint32_t w) { return w & 0xFFFFu; }
 DEV uint32_t pc_cnt(uint32_t w) { return w >> 16; }
 DEV uint32_t pc_of(uint32_t b, uint32_t k) { return b | (k << 16); }
+// Lane flags.  A block held in registers (one item per lane: load_block's `it`, D.cit) carries
+// each item's liveness and visibility in the two top bits of its lane's word: item ids are below
+// 2^30 (run_doc checks), and a visible item is live, so a lane holds 0 (not inserted yet, or past
+// the block's count), F_LIVE (deleted) or F_LIVE | F_VIS (visible).  Both tests are one vector
+// compare, the flags move with the items when an insert shifts them (one ds_bpermute), and the
+// 64-bit mask algebra the scalar unit used to do for every insert is gone; a wave-uniform mask is
+// made by ballot only where a scalar consumer remains (the m2 words, the hit test, select_vis).
+// Memory never sees the flags: rows, pc[] indices and origins are masked with ID_MASK.
+constexpr uint32_t F_LIVE = 1u << 31, F_VIS = 1u << 30, ID_MASK = F_VIS - 1u;
+DEV bool f_vis(uint32_t it) { return it >= (F_LIVE | F_VIS); }
+DEV bool f_live(uint32_t it) { return int32_t(it) < 0; }
+DEV uint32_t f_of_count(uint32_t k) { return k == 1u ? (F_LIVE | F_VIS) : (k ? F_LIVE : 0u); }
 
 // Per-document state (pc, masks) is only ever read and written by its own wave with plain
 // accesses, which the CU keeps coherent for that wave: plain loads may hit L1.  The HBM-index
@@ -155,11 +167,12 @@ struct Doc {
                                   // violation ends the document with ErrCapacity
     uint64_t prof[P_N];
     uint32_t doc;
-    // the block the last insert / delete left behind, in registers (items lane by lane, masks):
-    // typing keeps hitting it, so the next command skips its load.  Memory always holds the
-    // same state (every change is stored); a toggle touching the block drops it.
+    // the block the last insert / delete left behind, in registers (items lane by lane with
+    // their lane flags, and the visible mask those flags ballot to): typing keeps hitting it, so
+    // the next command skips its load.  Memory always holds the same state (every change is
+    // stored); a toggle touching the block drops it.
     uint32_t cb, cit;
-    u64 cmv, cml;
+    u64 cmv;
     // flat tier: the visible items before block cb (PRE_NONE: unknown, or no cached block) and
     // cb's position in ord[].  An edit whose position falls among cb's visible items skips the
     // index scan (find_vis); a retreat/advance pass that leaves cb cached adds the flips in
@@ -345,12 +358,12 @@ DEV bool find_vis(Doc &D, uint32_t p, Found &f) {
     return true;
 }
 
-// Slot of the k-th set bit of a wave-uniform mask.
-DEV uint32_t select_bit(u64 m, uint32_t k) {
-    const uint32_t l = lane();
-    const bool set = (m >> l) & 1ull;
-    const uint32_t before = uint32_t(__popcll(m & lanes_below(l)));
-    return ctz(BALLOT(set && before == k));
+// Slot of the k-th visible item of a block in registers (`it` with its lane flags, mv the mask
+// they ballot to); NONE when the block has no such item.  A lane's rank is its mbcnt against mv,
+// and a lane that is not visible takes a rank no k equals: one compare, no lane-mask AND.
+DEV uint32_t select_vis(uint32_t it, u64 mv, uint32_t k) {
+    const uint32_t rank = f_vis(it) ? bits_below(mv) : NONE;
+    return uint32_t(__ffsll(BALLOT(rank == k)) - 1);
 }
 
 // First block after b (document order) with a live item, or NONE (origin_right search,
@@ -466,13 +479,15 @@ DEV void split_sb(Doc &D, uint32_t S) {
     D.nsb++;
 }
 
-// Split the full block b (items in `it` lane by lane, masks mv / ml) at slot c: items [c, 64)
-// move to a new block b2 placed right after b in its superblock.
+// Split the full block b (items with their lane flags in `itf`, lane by lane) at slot c: items
+// [c, 64) move to a new block b2 placed right after b in its superblock.
 template <int L, bool XF>
-DEV uint32_t split_block(Doc &D, uint32_t b, uint32_t c, uint32_t it, u64 mv, u64 ml) {
+DEV uint32_t split_block(Doc &D, uint32_t b, uint32_t c, uint32_t itf) {
     const uint32_t l = lane();
     if (D.nb >= D.max_blocks) { fail(D, ErrCapacity, 12); return 0; }
     const uint32_t b2 = D.nb;
+    const uint32_t it = itf & ID_MASK;
+    const u64 mv = BALLOT(f_vis(itf)), ml = BALLOT(f_live(itf));   // both blocks' m2 words and counts
     u64 mu = 0, mu_lo = 0, mu_hi = 0;
     if (XF) {
         mu = U64(ld(D.mup + b));
@@ -579,9 +594,9 @@ DEV uint32_t up_rank(Doc &D, uint32_t b, uint32_t s) {
 }
 
 // Insert the run [lv, lv+k) before slot s of block b (all new items visible).  `it` holds the
-// block's items lane by lane (lanes >= the block count are don't-care); mv / ml its masks.
+// block's items with their lane flags, lane by lane (lanes >= the block count hold 0).
 template <int L, bool PROF, bool XF>
-DEV void insert_run(Doc &D, uint32_t b, uint32_t s, uint32_t it, u64 mv, u64 ml, uint32_t lv, uint32_t k,
+DEV void insert_run(Doc &D, uint32_t b, uint32_t s, uint32_t it, uint32_t lv, uint32_t k,
                     uint32_t ol, uint32_t orr, uint32_t tph, uint32_t c_in) {
     // flat tier: the caller set D.cpre / D.cpos for b.  They stay true of the block the run ends
     // in if that is b: a split puts the new block after b.
@@ -595,15 +610,14 @@ DEV void insert_run(Doc &D, uint32_t b, uint32_t s, uint32_t it, u64 mv, u64 ml,
         for (uint32_t j = l; j < k0; j += 64) D.xf[lv0 + j] = r0 + j;
     }
     if (!XF && c_in != NONE && c_items(c_in) + k <= BLK) {
-        // the common case as straight-line code: the run fits the block (no split, one round)
+        // the common case as straight-line code: the run fits the block (no split, one round).
+        // The shifted items bring their flags along; the new ones are born visible.
         const uint32_t shifted = shfl(it, l >= k ? l - k : l);
-        it = l < s ? it : (l < s + k ? lv + (l - s) : shifted);
-        D.items[size_t(b) * BLK + l] = it;
-        if (l >= s && l < s + k) st(D.pc + it, pc_of(b, 1u));
-        const u64 low = lanes_below(s);
-        const u64 ins = lanes_below(k) << s;
-        mv = k == 64 ? ins : ((mv & low) | ((mv & ~low) << k) | ins);
-        ml = k == 64 ? ins : ((ml & low) | ((ml & ~low) << k) | ins);
+        const uint32_t j = l - s;   // (unsigned: a lane below s is far past k)
+        it = l < s ? it : (j < k ? (lv + j) | F_LIVE | F_VIS : shifted);
+        D.items[size_t(b) * BLK + l] = it & ID_MASK;
+        if (j < k) st(D.pc + (lv + j), pc_of(b, 1u));
+        const u64 mv = BALLOT(f_vis(it)), ml = BALLOT(f_live(it));
         st(D.m2 + 2 * size_t(b) + (l & 1u), (l & 1u) ? ml : mv);
         if (tph == NONE) tph = L == IX_FLAT ? U(uint32_t(D.opos16[b]) >> 6) : U(ix<L>(D.sbpos + (opos_of<L>(D, b) >> 6)));
         if (l == 0) {
@@ -617,7 +631,7 @@ DEV void insert_run(Doc &D, uint32_t b, uint32_t s, uint32_t it, u64 mv, u64 ml,
         }
         if (l < k) D.ao[lv + l] = u64(l == 0 ? ol : lv + l - 1) | (u64(orr) << 32);
         fence_wave();
-        D.cb = b; D.cit = it; D.cmv = mv; D.cml = ml;
+        D.cb = b; D.cit = it; D.cmv = mv;
         return;
     }
     while (k > 0) {   // each round inserts >= 1 item or splits (bounded by max_blocks)
@@ -628,18 +642,16 @@ DEV void insert_run(Doc &D, uint32_t b, uint32_t s, uint32_t it, u64 mv, u64 ml,
         if (bc == BLK) {
             const uint64_t t0 = tick<PROF>();
             const uint32_t cut = cut_point<L>(s);
-            const uint32_t b2 = split_block<L, XF>(D, b, cut, it, mv, ml);
+            const uint32_t b2 = split_block<L, XF>(D, b, cut, it);
             if (D.err) return;
             tph = NONE;   // a split may move superblocks in the top order
-            if (s > cut || cut == BLK) {
+            if (s > cut || cut == BLK) {   // on in the new block: its items, the lanes past them empty
                 b = b2;
                 s -= cut;
-                it = shfl(it, (l + cut) & 63u);
-                mv = cut >= 64 ? 0ull : mv >> cut;
-                ml = cut >= 64 ? 0ull : ml >> cut;
+                const uint32_t up = shfl(it, (l + cut) & 63u);
+                it = l + cut < BLK ? up : 0u;
             } else {
-                mv &= lanes_below(cut);
-                ml &= lanes_below(cut);
+                it = l < cut ? it : 0u;
             }
             if (PROF) { D.prof[P_SPLIT] += tick<PROF>() - t0; D.prof[P_N_SPLIT]++; }
             continue;
@@ -650,16 +662,16 @@ DEV void insert_run(Doc &D, uint32_t b, uint32_t s, uint32_t it, u64 mv, u64 ml,
         // the block after the insert, lane = slot: the row from the insert point on is written
         // with one store; only the new items get a block in pos[] (shifted ones stay put)
         const uint32_t shifted = shfl(it, l >= m ? l - m : l);
-        it = l < s ? it : (l < s + m ? lv + (l - s) : shifted);
-        items[l] = it;   // the whole row: slots past the count are don't-care
-        if (l >= s && l < s + m) st(D.pc + it, pc_of(b, 1u));
+        const uint32_t j = l - s;
+        it = l < s ? it : (j < m ? (lv + j) | F_LIVE | F_VIS : shifted);
+        items[l] = it & ID_MASK;   // the whole row: slots past the count are don't-care
+        if (j < m) st(D.pc + (lv + j), pc_of(b, 1u));
         if (PROF) { const uint64_t t = tick<PROF>(); D.prof[P_R1] += t - tr; tr = t; }
-        const u64 low = lanes_below(s);
-        const u64 ins = lanes_below(m) << s;
-        mv = m == 64 ? ins : ((mv & low) | ((mv & ~low) << m) | ins);
-        ml = m == 64 ? ins : ((ml & low) | ((ml & ~low) << m) | ins);
+        const u64 mv = BALLOT(f_vis(it)), ml = BALLOT(f_live(it));
         st(D.m2 + 2 * size_t(b) + (l & 1u), (l & 1u) ? ml : mv);   // every lane: no exec branch
         if (XF) {
+            const u64 low = lanes_below(s);
+            const u64 ins = lanes_below(m) << s;
             u64 mu = U64(ld(D.mup + b));
             mu = m == 64 ? ins : ((mu & low) | ((mu & ~low) << m) | ins);
             if (l == 0) st(D.mup + b, mu);
@@ -682,7 +694,7 @@ DEV void insert_run(Doc &D, uint32_t b, uint32_t s, uint32_t it, u64 mv, u64 ml,
         k -= m;
         s += m;
     }
-    D.cb = b; D.cit = it; D.cmv = mv; D.cml = ml;   // block state after the run
+    D.cb = b; D.cit = it; D.cmv = BALLOT(f_vis(it));   // block state after the run
     if (PC && b != b_in) D.cpre = PRE_NONE;
     const uint64_t t3 = tick<PROF>();
     for (uint32_t j0 = 0; j0 < k0; j0 += 64) {   // wave-uniform loop, masked store
@@ -801,11 +813,13 @@ DEV void yjs_scan(Doc &D, uint32_t &b, uint32_t &s, uint32_t rb, uint32_t rs, ui
     s = U(s);
 }
 
-// Items and masks of block b (packed count c) into registers: items lane by lane, masks
-// wave-uniform.  A block whose masks a retreat/advance pass invalidated (DIRTY) gets them
-// rebuilt from the items' counts and stored back clean.
+// Items of block b (packed count c) into registers, lane by lane with their lane flags, and the
+// visible mask the flags ballot to (wave-uniform; the live mask has no scalar consumer past the
+// m2 store).  A block whose masks a retreat/advance pass invalidated (DIRTY) takes the flags
+// straight from its items' counts and gets its masks stored back clean; a clean block's flags
+// are its two m2 words shifted by the lane id.
 template <int L, bool PROF = false>
-DEV void load_block(Doc &D, uint32_t b, uint32_t c, uint32_t &it, u64 &mv, u64 &ml) {
+DEV void load_block(Doc &D, uint32_t b, uint32_t c, uint32_t &it, u64 &mv) {
     const uint32_t l = lane();
     const uint32_t bc = c_items(c);
     if (PROF) { D.prof[P_N_LOAD]++; if (c & C_DIRTY) D.prof[P_N_DIRTY]++; }
@@ -813,15 +827,18 @@ DEV void load_block(Doc &D, uint32_t b, uint32_t c, uint32_t &it, u64 &mv, u64 &
     it = l < bc ? it0 : 0;
     if (c & C_DIRTY) {
         const uint32_t k = pc_cnt(ld(D.pc + it));   // lanes past the count read item 0's word
-        mv = BALLOT(l < bc && k == 1u);
-        ml = BALLOT(l < bc && k != 0u);
+        it |= l < bc ? f_of_count(k) : 0u;
+        mv = BALLOT(f_vis(it));
+        const u64 ml = BALLOT(f_live(it));
         st(D.m2 + 2 * size_t(b) + (l & 1u), (l & 1u) ? ml : mv);
         if (l == 0) D.cnt[b] = c & ~C_DIRTY;
         fence_wave();
     } else {
         const u64 x = ld(D.m2 + 2 * size_t(b) + (l & 1u));
         mv = rdl64(x, 0);
-        ml = rdl64(x, 1);
+        const u64 ml = rdl64(x, 1);
+        // (bits at or above the count are clear in both words: the row's stale slots get no flag)
+        it |= (uint32_t(mv >> l) & 1u) << 30 | (uint32_t(ml >> l) & 1u) << 31;
     }
 }
 
@@ -863,35 +880,36 @@ DEV void do_insert(Doc &D, uint32_t lv, uint32_t k, uint32_t pos) {
     const uint32_t bc = c_items(c0);
     uint32_t cb = c0 & ~C_DIRTY;   // b's packed counts once its masks are current
     uint32_t it;
-    u64 mv, ml;
-    if (b == D.cb) { it = D.cit; mv = D.cmv; ml = D.cml; }
-    else load_block<L, PROF>(D, b, c0, it, mv, ml);
+    u64 mv;
+    if (b == D.cb) { it = D.cit; mv = D.cmv; }
+    else load_block<L, PROF>(D, b, c0, it, mv);
     uint32_t s = 0, ol = ROOT_ID;
     if (pos) {
-        const uint32_t s0 = select_bit(mv, kk);
+        const uint32_t s0 = select_vis(it, mv, kk);
         if (s0 >= bc) { fail(D, ErrCheckout, 13); return; }
-        ol = U(rdl(it, s0));
+        ol = U(rdl(it, s0)) & ID_MASK;
         s = s0 + 1;
     }
     if (PROF) { const uint64_t t = tick<PROF>(); D.prof[P_BLOAD] += t - tp; tp = t; }
-    // origin_right: first live item at or after the cursor (possibly a deleted one)
-    const u64 mlr = s >= 64 ? 0ull : (ml & (~0ull << s));
+    // origin_right: first live item at or after the cursor (possibly a deleted one).  A live lane
+    // holds its slot + 1 and any other lane 0: one compare against the cursor, one ballot
+    const u64 mlr = BALLOT((uint32_t(int32_t(it) >> 31) & (lane() + 1u)) > s);
     uint32_t rb, rs, orr;
     bool direct;
     if (mlr) {
         rb = b;
         rs = ctz(mlr);
-        orr = U(rdl(it, rs));
+        orr = U(rdl(it, rs)) & ID_MASK;
         direct = rs == s;
     } else {
         rb = next_live_block<L>(D, b);
         if (D.err) return;
         if (rb != NONE) {
             uint32_t rit;
-            u64 rmv, rml;
-            load_block<L, PROF>(D, rb, U(ix<L>(D.cnt + rb)), rit, rmv, rml);
-            rs = ctz(rml);
-            orr = U(rdl(rit, rs));
+            u64 rmv;
+            load_block<L, PROF>(D, rb, U(ix<L>(D.cnt + rb)), rit, rmv);
+            rs = ctz(BALLOT(f_live(rit)));   // (the index says the block has a live item)
+            orr = U(rdl(rit, rs)) & ID_MASK;
         } else {
             rs = 0;
             orr = END_ID;
@@ -912,8 +930,8 @@ DEV void do_insert(Doc &D, uint32_t lv, uint32_t k, uint32_t pos) {
         if (D.err) return;
         if (b != b0) {
             cb = U(ix<L>(D.cnt + b));
-            if (b == D.cb) { it = D.cit; mv = D.cmv; ml = D.cml; }
-            else load_block<L, PROF>(D, b, cb, it, mv, ml);
+            if (b == D.cb) { it = D.cit; mv = D.cmv; }
+            else load_block<L, PROF>(D, b, cb, it, mv);
             cb &= ~C_DIRTY;
             tph = NONE;
             if (PC) D.cpre = PRE_NONE;   // (the items before the new block are not counted)
@@ -921,7 +939,7 @@ DEV void do_insert(Doc &D, uint32_t lv, uint32_t k, uint32_t pos) {
         if (PROF) { const uint64_t t = tick<PROF>(); D.prof[P_YJS] += t - tp; tp = t; D.prof[P_N_YJS]++; }
     }
     const uint64_t sp0 = PROF ? D.prof[P_SPLIT] : 0;
-    insert_run<L, PROF, XF>(D, b, s, it, mv, ml, lv, k, ol, orr, tph, cb);
+    insert_run<L, PROF, XF>(D, b, s, it, lv, k, ol, orr, tph, cb);
     if (PROF) D.prof[P_RUN] += tick<PROF>() - tp - (D.prof[P_SPLIT] - sp0);
 }
 
@@ -950,14 +968,15 @@ DEV void do_delete(Doc &D, uint32_t lv, uint32_t n, uint32_t pos, bool fwd) {
         const uint32_t b = f.b, kk = f.k, tpos = f.tp;
         const uint32_t c0 = L == IX_FLAT && f.c != NONE ? f.c : U(ix<L>(D.cnt + b));
         uint32_t it;
-        u64 mv, ml;
-        if (b == D.cb) { it = D.cit; mv = D.cmv; ml = D.cml; }
-        else load_block<L, PROF>(D, b, c0, it, mv, ml);
+        u64 mv;
+        if (b == D.cb) { it = D.cit; mv = D.cmv; }
+        else load_block<L, PROF>(D, b, c0, it, mv);
         const uint32_t c = c0 & ~C_DIRTY;   // load_block left the block clean
         const uint32_t avail = c_vis(c) - kk;
         const uint32_t take = min(avail, n - j0);
-        const uint32_t r = uint32_t(__popcll(mv & lanes_below(l)));
-        const bool sel = ((mv >> l) & 1ull) && r >= kk && r < kk + take;
+        // a visible lane's rank past kk (a lane that is not visible: past any take), one compare
+        const uint32_t r = bits_below(mv);
+        const bool sel = (f_vis(it) ? r - kk : NONE) < take;
         const u64 selm = BALLOT(sel);
         if (uint32_t(__popcll(selm)) != take || take == 0) { fail(D, ErrCheckout, 15); return; }
         u64 mu = 0;
@@ -969,8 +988,8 @@ DEV void do_delete(Doc &D, uint32_t lv, uint32_t n, uint32_t pos, bool fwd) {
         if (sel) {
             const uint32_t j = j0 + (r - kk);
             const uint32_t dlv = fwd ? lv + j : lv + n - 1 - j;
-            st(D.pc + it, pc_of(b, 2u));   // visible (count 1) -> deleted once
-            *reinterpret_cast<uint32_t *>(D.ao + dlv) = it;
+            st(D.pc + (it & ID_MASK), pc_of(b, 2u));   // visible (count 1) -> deleted once
+            *reinterpret_cast<uint32_t *>(D.ao + dlv) = it & ID_MASK;
             if (XF) {
                 // LV order applies a forward run left to right (the run's items to the left are
                 // already gone) and a backspace run right to left (the ones to the left, in
@@ -993,7 +1012,7 @@ DEV void do_delete(Doc &D, uint32_t lv, uint32_t n, uint32_t pos, bool fwd) {
             }
         }
         fence_wave();
-        D.cb = b; D.cit = it; D.cmv = mv & ~selm; D.cml = ml;
+        D.cb = b; D.cit = sel ? it & ~F_VIS : it; D.cmv = mv & ~selm;   // deleted: live, not visible
         j0 += take;
     }
 }
@@ -1661,6 +1680,14 @@ DEV uint32_t check_invariants(Doc &D, DocResult *res) {
         if (U(before) != D.cpre) return 212;
         if (uint32_t(__popcll(D.cmv)) != c_vis(U(D.cnt[D.cb]))) return 213;
     }
+    if (D.cb != NONE) {   // the cached block's lane flags against flags recomputed from the counts
+        if (D.cb >= D.nb) return 214;
+        const uint32_t cnt = c_items(U(ix<L>(D.cnt + D.cb)));
+        const uint32_t i2 = l < cnt ? D.items[size_t(D.cb) * BLK + l] : 0u;
+        const uint32_t k = l < cnt && i2 < n_ids ? pc_cnt(ld(D.pc + i2)) : 0u;
+        const uint32_t want = l < cnt ? (i2 | f_of_count(k)) : 0u;
+        if (BALLOT(D.cit != want) || BALLOT(f_vis(D.cit)) != D.cmv) return 214;
+    }
     return 0;
 }
 
@@ -1671,6 +1698,10 @@ DEV void run_doc(Doc &D) {
     D.nsb = 1;
     D.err = 0;
     D.site = 0;
+    // Item ids -- the LVs and a segment's placeholders after them -- stay below 2^30: the two bits
+    // above are the lane flags.  (Prep rejects n_lv >= 2^30 already; no test stages a document of
+    // that size, so none covers this guard.)
+    if (D.n_lv >= F_VIS || D.n_lv < U(vld(&D.desc->n_lv))) fail(D, ErrCapacity, 33);
     // a segment (cut replay) applies its LV range's commands only
     const uint32_t seg_lo = U(vld(&D.desc->seg_lo)), seg_hi = U(vld(&D.desc->seg_hi));
     if (!XF && (seg_lo != 0 || seg_hi != NONE)) {
@@ -1699,7 +1730,7 @@ DEV void run_doc(Doc &D) {
     }
     D.cb = NONE;
     D.cit = 0;
-    D.cmv = D.cml = 0;
+    D.cmv = 0;
     D.cpre = PRE_NONE;
     D.cpos = 0;
     if (PROF) for (int i = 0; i < P_N; i++) D.prof[i] = 0;
