@@ -50,6 +50,16 @@ pub struct dtgpu_doc_result {
     pub text_hash: u64,
     pub n_lv: u64,
 }
+/// One run of a document's blame (include/dtgpu.h `dtgpu_blame_run`): `len` characters of the text,
+/// character k inserted by LV `lv + k` = (`agent`, `seq + k`).
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug, PartialEq, Eq)]
+pub struct dtgpu_blame_run {
+    pub lv: u32,
+    pub len: u32,
+    pub agent: u32,
+    pub seq: u32,
+}
 #[repr(C)]
 #[derive(Default, Clone, Copy, Debug)]
 pub struct dtgpu_batch_opts {
@@ -68,6 +78,7 @@ pub const DTGPU_OPT_NO_SPLIT: u32 = 8;
 pub const DTGPU_OPT_NO_CRITICAL: u32 = 16;
 pub const DTGPU_OPT_DEBUG: u32 = 32;
 pub const DTGPU_OPT_PASS_MARK: u32 = 64;
+pub const DTGPU_OPT_BLAME: u32 = 128;
 pub type dtgpu_status = c_int;
 pub const DTGPU_OK: dtgpu_status = 0;
 // EncodeOptions (src/list/encoding/encode_oplog.rs:88-130) as dtgpu_oplog_encode flags
@@ -160,6 +171,13 @@ extern "C" {
     pub fn dtgpu_patches_profile(p: *const dtgpu_patches, i: usize, out: *mut u32) -> dtgpu_status;
     pub fn dtgpu_patches_free(p: *mut dtgpu_patches);
     pub fn dtgpu_batch_create_decoded(dec: *mut dtgpu_decoded, out: *mut *mut dtgpu_batch) -> dtgpu_status;
+    pub fn dtgpu_batch_create_decoded_opts(dec: *mut dtgpu_decoded, opts: *const dtgpu_batch_opts,
+                                           out: *mut *mut dtgpu_batch) -> dtgpu_status;
+    // batched blame (DTGPU_OPT_BLAME): each document's text as runs (lv, len, agent, seq)
+    pub fn dtgpu_batch_blame(b: *const dtgpu_batch, i: usize, runs: *mut dtgpu_blame_run, cap: usize,
+                             n: *mut usize) -> dtgpu_status;
+    pub fn dtgpu_batch_blame_agents(b: *const dtgpu_batch, i: usize, names: *mut u8, cap: usize, n: *mut usize) -> dtgpu_status;
+    pub fn dtgpu_batch_blame_stats(b: *const dtgpu_batch, out: *mut u64) -> dtgpu_status;
     // version summaries: what a peer that knows no local LVs holds (src/causalgraph/summary.rs:119-264)
     pub fn dtgpu_oplog_summarize(oplog: *const dtgpu_oplog, names: *mut u8, names_cap: usize, name_off: *mut usize,
                                  range_off: *mut usize, entry_cap: usize, ranges: *mut u64, range_cap: usize,

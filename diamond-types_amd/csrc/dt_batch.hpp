@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/dtgpu.h"
+#include "dt_blame.hpp"
 #include "dt_cut.hpp"
 #include "dt_decoded.hpp"
 #include "dt_devbuf.hpp"
@@ -58,6 +59,8 @@ struct Settings {
     bool prep_check = false;   // the bounds-checked prep kernel
     bool pass_mark = false;    // every pass opens with pass_mark_kernel (tools/traffic.py)
     bool plan_prof = false, enc_prof = false;
+    bool blame = false;        // the batch also produces each document's blame (dt_blame.hpp): every uncut
+                               // tracker document a segment group of one, no late cuts, no late pipeline
     uint32_t enc_lds_text = 0;
 };
 Settings settings_for(const dtgpu_batch_opts *o);
@@ -208,6 +211,29 @@ struct dtgpu_batch {
     DevBuf<uint32_t> f_bad, f_pa, f_pb, f_ca, f_cb, f_boff;
     dtgpu::FFParams ff{};
     bool pass_mark = false;   // DTGPU_PASS_MARK at staging: every pass opens with pass_mark_kernel
+
+    // blame batches (DTGPU_OPT_BLAME, dt_blame.hpp): seg_groups holds the cut groups (n_cut_groups,
+    // what the device cut planning plans), then the uncut tracker documents' groups of one.  Every
+    // pass counts the runs; the first blame read after it sizes the run arena from the counts,
+    // emits the runs and copies them and the documents' statuses back (Blame::h_*).
+    uint32_t n_cut_groups = 0;
+    struct Blame {
+        std::vector<dtgpu::BlameDoc> docs;
+        DevBuf<dtgpu::BlameDoc> d_docs;
+        DevBuf<uint32_t> d_bits, d_len, d_count;
+        DevBuf<uint64_t> d_off;
+        DevBuf<dtgpu::BlameRun> d_runs;
+        dtgpu::BlameParams p{};
+        std::vector<std::vector<uint8_t>> names;   // host-staged: per document, the agent_names export
+        hipEvent_t ev[4] = {};                     // around the counting kernels, around the emit
+        uint64_t pass = 0, read = 0;               // passes launched; the pass the host copies are of
+        std::vector<uint32_t> h_count, h_status;
+        std::vector<uint64_t> h_off;
+        std::vector<dtgpu::BlameRun> h_runs;
+        uint64_t stats[4] = {};
+        ~Blame() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+    };
+    std::unique_ptr<Blame> blame;
 
     // batched encoder (dtgpu_batch_encode): per-document descriptors, scratch, output
     std::vector<dtgpu::EncDesc> e_desc;

@@ -359,6 +359,7 @@ dtgpu_status dtgpu_batch_create_from_oplogs(const dtgpu_oplog *const *oplogs, si
 dtgpu_status dtgpu_batch_create_xf(const dtgpu_oplog *const *oplogs, size_t n, const dtgpu_batch_opts *opts,
                                    dtgpu_batch **out) {
     if (!out || (n && !oplogs)) return DTGPU_ERR_ARG;
+    if (opts && (opts->flags & DTGPU_OPT_BLAME)) return DTGPU_ERR_ARG;   // blame is a checkout batch's
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return DTGPU_ERR_NO_DEVICE;
     std::vector<Prepared> prep(n);
@@ -379,13 +380,16 @@ dtgpu_status dtgpu_batch_create_device(const uint8_t *const *docs, const size_t 
     return stage_device(dh, opts, out);
 }
 
-dtgpu_status dtgpu_batch_create_decoded(dtgpu_decoded *dec, dtgpu_batch **out) {
+dtgpu_status dtgpu_batch_create_decoded_opts(dtgpu_decoded *dec, const dtgpu_batch_opts *opts, dtgpu_batch **out) {
     if (!dec || !out) return DTGPU_ERR_ARG;
     if (!dec->stream && hipStreamCreateWithFlags(&dec->stream, hipStreamNonBlocking) != hipSuccess) {
         dtgpu_decode_free(dec);   // consumed on failure too (dtgpu.h)
         return DTGPU_ERR_HIP;
     }
-    return stage_device(dec, nullptr, out);
+    return stage_device(dec, opts, out);
+}
+dtgpu_status dtgpu_batch_create_decoded(dtgpu_decoded *dec, dtgpu_batch **out) {
+    return dtgpu_batch_create_decoded_opts(dec, nullptr, out);
 }
 
 dtgpu_status dtgpu_batch_checkout(const uint8_t *const *docs, const size_t *lens, size_t n,

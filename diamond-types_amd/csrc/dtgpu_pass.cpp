@@ -99,7 +99,10 @@ int reset_handback(dtgpu_batch *B, hipStream_t s) {
 // The tail of every tracker pass on s: the HBM tier (its own documents and whatever the LDS tiers
 // handed back), then the cut documents' texts joined from their segments'.
 int replay_hbm_and_combine(dtgpu_batch *B, hipStream_t s) {
-    const int e = launch_replay_hbm(B->large, s, instrumented(B));
+    int e = launch_replay_hbm(B->large, s, instrumented(B));
+    // a blame batch: the final lists' lengths, before the combine step rewrites the results of
+    // the groups of one
+    if (!e && B->blame) e = launch_blame_len(B->blame->p, s);
     return e ? e : launch_combine(B->comb, s);
 }
 // The replay of a whole pass, or the main pipeline's of a split pass (skip_tier: replayed by the
@@ -254,9 +257,111 @@ int launch_pass(dtgpu_batch *B, hipStream_t s, const PassMarks &m = {}) {
     return replay_all(B, s, B->split_tier);
 }
 
+// A blame batch's pass ends with the boundary bitmaps and the run counts (dt_blame.hip), on s
+// after everything else of the pass; the runs themselves are emitted by the first blame read.
+int launch_blame_pass(dtgpu_batch *B, hipStream_t s) {
+    if (!B->blame) return OK;
+    dtgpu_batch::Blame &M = *B->blame;
+    if (hipEventRecord(M.ev[0], s) != hipSuccess || launch_blame_count(M.p, s) || hipEventRecord(M.ev[1], s) != hipSuccess)
+        return ErrHip;
+    M.pass++;
+    return OK;
+}
+// The runs of the last pass on the host: the counts read back, the run arena sized from them,
+// the emit kernel, and one copy of the runs and the documents' statuses.
+dtgpu_status read_blame(const dtgpu_batch *B) {
+    dtgpu_batch::Blame &M = *B->blame;
+    if (M.read == M.pass && M.pass) return DTGPU_OK;
+    if (!M.pass) return DTGPU_ERR_ARG;   // no pass has run
+    if (hipSetDevice(B->device) != hipSuccess) return DTGPU_ERR_HIP;
+    hipStream_t s = B->stream;
+    const size_t n = B->n;
+    M.h_count.assign(2 * std::max<size_t>(n, 1), 0);
+    std::vector<DocResult> dr(n);
+    DTGPU_CK(hipStreamSynchronize(s));
+    DTGPU_CK(hipEventSynchronize(M.ev[1]));   // (a pass on the caller's stream)
+    if (n) {
+        DTGPU_CK(hipMemcpyAsync(M.h_count.data(), M.d_count.p, 2 * n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        DTGPU_CK(hipMemcpyAsync(dr.data(), B->d_results.p, n * sizeof(DocResult), hipMemcpyDeviceToHost, s));
+    }
+    DTGPU_CK(hipStreamSynchronize(s));
+    M.h_off.assign(n + 1, 0);
+    M.h_status.assign(n, 0);
+    uint64_t chars = 0;
+    for (size_t i = 0; i < n; i++) {
+        M.h_status[i] = B->host_status[i] != OK ? B->host_status[i] : dr[i].status;
+        if (M.h_status[i] != OK) M.h_count[i] = M.h_count[n + i] = 0;
+        M.h_off[i + 1] = M.h_off[i] + M.h_count[i];
+        chars += M.h_count[n + i];
+    }
+    const uint64_t total = M.h_off[n];
+    if (!M.d_runs.p || M.d_runs.n < total) DTGPU_CK(M.d_runs.alloc(total));   // (a batch of empty texts: one slot)
+    if (!M.d_off.p || M.d_off.n < n + 1) DTGPU_CK(M.d_off.alloc(n + 1));
+    DTGPU_CK(hipMemcpyAsync(M.d_off.p, M.h_off.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    DTGPU_CK(hipMemsetAsync(M.d_runs.p, 0, std::max<uint64_t>(total, 1) * sizeof(BlameRun), s));
+    BlameParams p = M.p;
+    p.run_off = M.d_off.p;
+    p.runs = M.d_runs.p;
+    DTGPU_CK(hipEventRecord(M.ev[2], s));
+    if (total && launch_blame_emit(p, s)) return DTGPU_ERR_HIP;
+    DTGPU_CK(hipEventRecord(M.ev[3], s));
+    M.h_runs.assign(total, BlameRun{});
+    if (total) DTGPU_CK(hipMemcpyAsync(M.h_runs.data(), M.d_runs.p, total * sizeof(BlameRun), hipMemcpyDeviceToHost, s));
+    DTGPU_CK(hipStreamSynchronize(s));
+    float t0 = 0, t1 = 0;
+    DTGPU_CK(hipEventElapsedTime(&t0, M.ev[0], M.ev[1]));
+    DTGPU_CK(hipEventElapsedTime(&t1, M.ev[2], M.ev[3]));
+    M.stats[0] = total;
+    M.stats[1] = chars;
+    M.stats[2] = uint64_t((t0 + t1) * 1000.0f + 0.5f);
+    M.stats[3] = 4 * uint64_t(B->d_src.n) + sizeof(BlameRun) * uint64_t(M.d_runs.n);
+    M.read = M.pass;
+    return DTGPU_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+dtgpu_status dtgpu_batch_blame(const dtgpu_batch *B, size_t i, dtgpu_blame_run *runs, size_t cap, size_t *n_out) {
+    if (!B || !B->blame || i >= B->n) return DTGPU_ERR_ARG;
+    if (B->host_status[i] != OK) { if (n_out) *n_out = 0; return dtgpu_status(B->host_status[i]); }
+    if (const dtgpu_status st = read_blame(B)) return st;
+    const dtgpu_batch::Blame &M = *B->blame;
+    if (n_out) *n_out = M.h_status[i] == OK ? M.h_count[i] : 0;
+    if (M.h_status[i] != OK) return dtgpu_status(M.h_status[i]);
+    if (!runs) return DTGPU_OK;
+    if (cap < M.h_count[i]) return DTGPU_ERR_ARG;
+    static_assert(sizeof(dtgpu_blame_run) == sizeof(BlameRun), "one layout");
+    if (M.h_count[i]) std::memcpy(runs, M.h_runs.data() + M.h_off[i], M.h_count[i] * sizeof(BlameRun));
+    return DTGPU_OK;
+}
+dtgpu_status dtgpu_batch_blame_agents(const dtgpu_batch *B, size_t i, uint8_t *names, size_t cap, size_t *n_out) {
+    if (!B || !B->blame || i >= B->n) return DTGPU_ERR_ARG;
+    if (B->host_status[i] != OK) { if (n_out) *n_out = 0; return dtgpu_status(B->host_status[i]); }
+    size_t n = 0;
+    if (B->dec) {   // device-staged: the decoder's agent table
+        if (hipSetDevice(B->device) != hipSuccess) return DTGPU_ERR_HIP;
+        n = dtgpu_decode_export(B->dec.get(), i, DTGPU_EXPORT_AGENT_NAMES, nullptr, 0);
+        if (n_out) *n_out = n;
+        if (!names) return DTGPU_OK;
+        if (cap < n) return DTGPU_ERR_ARG;
+        return dtgpu_decode_export(B->dec.get(), i, DTGPU_EXPORT_AGENT_NAMES, names, cap) == n ? DTGPU_OK : DTGPU_ERR_HIP;
+    }
+    const std::vector<uint8_t> &blob = B->blame->names[i];
+    n = blob.size();
+    if (n_out) *n_out = n;
+    if (!names) return DTGPU_OK;
+    if (cap < n) return DTGPU_ERR_ARG;
+    if (n) std::memcpy(names, blob.data(), n);
+    return DTGPU_OK;
+}
+dtgpu_status dtgpu_batch_blame_stats(const dtgpu_batch *B, uint64_t out[4]) {
+    if (!B || !B->blame || !out) return DTGPU_ERR_ARG;
+    if (const dtgpu_status st = read_blame(B)) return st;
+    for (int k = 0; k < 4; k++) out[k] = B->blame->stats[k];
+    return DTGPU_OK;
+}
 
 dtgpu_status dtgpu_batch_xf_positions(dtgpu_batch *B, size_t i, uint32_t *out, size_t cap, size_t *n_out) {
     if (!B || i >= B->n || !B->xf_mode) return DTGPU_ERR_ARG;
@@ -286,6 +391,7 @@ dtgpu_status dtgpu_batch_run_e2e_timed(dtgpu_batch *B, float ms[4]) {
     const int st = tracker_pass(B) ? launch_tracker(B, s, PassMarks{nullptr, B->ev0, B->ev_mid})
                                    : (mark(B->ev0, s) || mark(B->ev_mid, s) ? ErrHip : OK);
     if (st) return dtgpu_status(st);
+    if (launch_blame_pass(B, s)) return DTGPU_ERR_HIP;
     if (hipEventRecord(B->ev1, s) != hipSuccess) return DTGPU_ERR_HIP;
     if (hipEventSynchronize(B->ev1) != hipSuccess) return DTGPU_ERR_HIP;
     float td = 0, tp = 0, tl = 0, tr = 0;
@@ -426,6 +532,7 @@ dtgpu_status dtgpu_batch_run(dtgpu_batch *B, void *stream) {
                 B->split ? B->split_tier : -1, B->n_big, B->n_rest);
     }
     dtgpu_status st = dtgpu_status(launch_pass(B, reinterpret_cast<hipStream_t>(s)));
+    if (!st) st = dtgpu_status(launch_blame_pass(B, reinterpret_cast<hipStream_t>(s)));
     if (B->debug) {
         fprintf(stderr, "[dtgpu] launched status %d\n", int(st));
         hipError_t e = hipStreamSynchronize(reinterpret_cast<hipStream_t>(s));
@@ -443,6 +550,7 @@ dtgpu_status dtgpu_batch_run_timed(dtgpu_batch *B, float *ms) {
     hipStream_t s = B->stream;
     const bool prep = B->dec && !B->xf_mode;
     if (const int st = launch_pass(B, s, PassMarks{B->ev_prep, B->ev0, B->ev_mid})) return dtgpu_status(st);
+    if (launch_blame_pass(B, s)) return DTGPU_ERR_HIP;   // (a blame batch: inside the pass's time)
     if (hipEventRecord(B->ev1, s) != hipSuccess) return DTGPU_ERR_HIP;
     if (hipEventSynchronize(B->ev1) != hipSuccess) return DTGPU_ERR_HIP;
     float t = 0, tp = 0, tq = 0;
@@ -480,7 +588,7 @@ dtgpu_status dtgpu_batch_last_times(const dtgpu_batch *B, float out[3]) {
 size_t dtgpu_batch_segments(dtgpu_batch *B, size_t doc, uint32_t *out, size_t cap) {
     if (!B || doc >= B->n) return 0;
     for (const SegGroup &g : B->seg_groups) {
-        if (B->seg_docs[g.first] != doc) continue;
+        if (B->seg_docs[g.first] != doc || g.count < 2) continue;   // (a blame batch's group of one: replayed whole)
         if (hipSetDevice(B->device) != hipSuccess) return 0;
         for (uint32_t k = 0; k < g.count && k < cap; k++) {
             const uint32_t d = B->seg_docs[g.first + k];

@@ -21,6 +21,7 @@ Settings settings_for(const dtgpu_batch_opts *o) {
         c.critical = !(o->flags & DTGPU_OPT_NO_CRITICAL);
         c.debug = (o->flags & DTGPU_OPT_DEBUG) ? 1u : 0u;
         c.pass_mark = (o->flags & DTGPU_OPT_PASS_MARK) != 0;
+        c.blame = (o->flags & DTGPU_OPT_BLAME) != 0;
         if (o->seg_ops) c.seg_ops = o->seg_ops;
         if (o->seg_max) c.seg_max = o->seg_max;
         if (o->lds_fill) c.lds_fill = o->lds_fill;
@@ -56,6 +57,9 @@ Settings settings_for(const dtgpu_batch_opts *o) {
     x = c.tog_waves; num("DTGPU_TOG_WAVES", 0, 64, x); c.tog_waves = uint32_t(x);
     x = c.tog_mw_lds; num("DTGPU_TOG_MW_LDS", 0, UINT64_MAX, x); c.tog_mw_lds = uint32_t(std::min<uint64_t>(x, UINT32_MAX));
     x = 0; num("DTGPU_ENC_LDS_TEXT", 0, 24064, x); c.enc_lds_text = uint32_t(x);
+    // a blame batch is another product than the headline: one pipeline, and cuts only where a
+    // document is long (every uncut document is a segment group of one, dt_blame.hpp)
+    if (c.blame) c.late_pipe = c.seg_late = false;
     return c;
 }
 
@@ -476,6 +480,69 @@ void mark_critical(dtgpu_batch &B) {
     for (size_t k = 0; k < cost.size(); k++)
         if (cost[k] >= mx / 2) B.docs[unit[k]].flags |= DOC_CRITICAL;
 }
+// Blame batches (dt_blame.hpp): after the cut documents' groups, every uncut tracker document
+// (tier[i] != -2) becomes a segment group of one -- seg_lo = 0, seg_hi = ~0, seg_u = 0 as
+// reset_doc left them, a source list for its inserted characters -- so its replay writes its
+// visible items in document order (materialise_src) and the combine step its text.
+void add_blame_groups(dtgpu_batch &B, const std::vector<int> &tier, const std::vector<uint64_t> &n_ins, Totals &T) {
+    B.n_cut_groups = uint32_t(B.seg_groups.size());
+    if (!B.cfg.blame) return;
+    for (size_t i = 0; i < B.n; i++) {
+        DocDesc &d = B.docs[i];
+        if (tier[i] == -2 || d.src_off != ~0ull) continue;
+        d.src_off = T.src;
+        d.src_cap = uint32_t(n_ins[i]);
+        T.src += n_ins[i];
+        B.seg_groups.push_back(SegGroup{uint32_t(B.seg_docs.size()), 1});
+        B.seg_docs.push_back(uint32_t(i));
+    }
+}
+// The blame kernels' descriptors and scratch, once the arenas and the fast-forward layout exist.
+dtgpu_status stage_blame(dtgpu_batch &B, const Totals &T) {
+    if (!B.cfg.blame) return DTGPU_OK;
+    hipStream_t s = B.stream;
+    if (!B.blame) B.blame = std::make_unique<dtgpu_batch::Blame>();
+    dtgpu_batch::Blame &M = *B.blame;
+    M.docs.assign(B.n, BlameDoc{});
+    std::vector<uint32_t> last(B.n, 0xFFFFFFFFu);
+    for (const SegGroup &g : B.seg_groups) last[B.seg_docs[g.first]] = B.seg_docs[g.first + g.count - 1];
+    uint64_t bits = 0;
+    uint32_t n_ff = 0;
+    for (size_t i = 0; i < B.n; i++) {
+        BlameDoc &q = M.docs[i];
+        const DocDesc &d = B.docs[i];
+        const bool ff = B.ff_doc[i] != 0;
+        const uint32_t ffi = ff ? n_ff++ : 0;   // stage_ff lays the linear documents out in this order
+        if (B.host_status[i] != OK) continue;
+        q.arun_off = d.arun_off;
+        q.n_aruns = d.n_aruns;
+        q.n_lv = d.n_lv;
+        q.bits_off = bits;
+        bits += (uint64_t(d.n_lv) + 31) / 32;
+        if (ff) {
+            q.kind = BLAME_FF;
+            q.last = ffi;
+        } else if (last[i] != 0xFFFFFFFFu) {
+            q.kind = BLAME_TRACKER;
+            q.last = last[i];
+            q.src_off = B.docs[last[i]].src_off;
+            q.cap = B.docs[last[i]].src_cap;
+        }
+    }
+    DTGPU_CK(M.d_docs.upload(M.docs, s));
+    DTGPU_CK(M.d_bits.alloc(std::max<uint64_t>(bits, 1)));
+    DTGPU_CK(M.d_len.alloc(std::max<size_t>(B.n, 1)));
+    DTGPU_CK(M.d_count.alloc(2 * std::max<size_t>(B.n, 1)));
+    DTGPU_CK(hipMemsetAsync(M.d_len.p, 0, std::max<size_t>(B.n, 1) * sizeof(uint32_t), s));
+    for (hipEvent_t &e : M.ev) if (!e) DTGPU_CK(hipEventCreate(&e));
+    BlameParams &p = M.p;
+    p.docs = M.d_docs.p; p.n_docs = uint32_t(B.n);
+    p.aruns = B.d_aruns.p; p.src = B.d_src.p; p.results = B.d_results.p;
+    p.bits = M.d_bits.p; p.len = M.d_len.p; p.count = M.d_count.p;
+    p.ff_docs = B.f_docs.p; p.pa = B.f_pa.p; p.pb = B.f_pb.p; p.ca = B.f_ca.p; p.cb = B.f_cb.p;
+    M.stats[3] = 4 * T.src;   // bytes of the source-list arena; the run arena is added when it is sized
+    return DTGPU_OK;
+}
 // The replay's arenas, once every document and segment is laid out (after the upload of the
 // document descriptors): the tier lists, the per-LV, block, out and index arenas, the results, and
 // the segments' source-list arena and combine step.
@@ -591,6 +658,7 @@ dtgpu_status stage(std::vector<Prepared> &prep, const dtgpu_batch_opts *opts, dt
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return DTGPU_ERR_NO_DEVICE;
     auto B = std::make_unique<dtgpu_batch>();
     B->cfg = settings_for(opts);
+    if (xf) B->cfg.blame = false;   // (dtgpu_batch_create_xf refuses the option)
     B->device = opts ? opts->device : 0;
     const size_t n = prep.size();
     if (begin_batch(*B, n) != DTGPU_OK) return DTGPU_ERR_HIP;
@@ -678,6 +746,7 @@ dtgpu_status stage(std::vector<Prepared> &prep, const dtgpu_batch_opts *opts, dt
     std::vector<uint8_t> content;
     Totals T;
     std::vector<int> seg_tier(n, -2);          // replay tier per document (-2: not replayed)
+    std::vector<uint64_t> n_ins(n, 0);         // inserted characters per document
     for (size_t i = 0; i < n; i++) {
         Prepared &p = prep[i];
         B->host_status[i] = p.status;
@@ -689,6 +758,7 @@ dtgpu_status stage(std::vector<Prepared> &prep, const dtgpu_batch_opts *opts, dt
         d.arun_off = pdesc[i].arun_off * 4;
         if (p.status != OK) { pdesc[i].skip = 1; continue; }
         const DocFacts f = facts_of(p.log);
+        n_ins[i] = f.n_ins;
         // Host staging checks the block capacity before the fast-forward branch, device staging
         // (stage_device) after it: a linear document past the limit is ErrCapacity here and checks
         // out there.  A known inconsistency, kept as it is.
@@ -751,6 +821,7 @@ dtgpu_status stage(std::vector<Prepared> &prep, const dtgpu_batch_opts *opts, dt
             const std::vector<SegCut> cuts = plan_segments(si, sc);
             if (cuts.size() >= 2) add_segments(*B, i, cuts, seg_tier[i], T);
         }
+        add_blame_groups(*B, seg_tier, n_ins, T);
     }
     hcmds.resize(T.cmd);
     htlist.resize(T.tlist);
@@ -777,6 +848,15 @@ dtgpu_status stage(std::vector<Prepared> &prep, const dtgpu_batch_opts *opts, dt
         DTGPU_CK(B->f_ops.upload(quads, s));
         DTGPU_CK(stage_ff(*B, ffin, B->f_ops.p, B->d_cbyte.p, B->d_content.p, s));
     }
+    if (stage_blame(*B, T) != DTGPU_OK) return DTGPU_ERR_HIP;
+    if (B->blame) {   // the agent ids' names, as the agent_names export lays them out
+        B->blame->names.resize(n);
+        for (size_t i = 0; i < n; i++)
+            for (const std::string &nm : prep[i].log.agent_names) {
+                B->blame->names[i].push_back(uint8_t(nm.size()));
+                B->blame->names[i].insert(B->blame->names[i].end(), nm.begin(), nm.end());
+            }
+    }
     if (xf) {
         DTGPU_CK(B->d_mup.alloc(T.blk));
         DTGPU_CK(B->d_tup.alloc(T.blk + 2 * n));
@@ -800,6 +880,7 @@ dtgpu_status stage(std::vector<Prepared> &prep, const dtgpu_batch_opts *opts, dt
 dtgpu_status stage_device(dtgpu_decoded *dec, const dtgpu_batch_opts *opts, dtgpu_batch **out, XfStage *xf) {
     auto B = std::make_unique<dtgpu_batch>();
     B->cfg = settings_for(opts);
+    if (xf) B->cfg.blame = false;
     B->device = dec->device;
     B->dec.reset(dec);
     dtgpu_decoded &Dd = *B->dec;
@@ -932,6 +1013,7 @@ dtgpu_status stage_device(dtgpu_decoded *dec, const dtgpu_batch_opts *opts, dtgp
     // ---- replay layout ---------------------------------------------------------------------------
     Totals T;
     std::vector<int> seg_tier(n, -2);          // replay tier per document (-2: not replayed)
+    std::vector<uint64_t> n_ins(n, 0);         // inserted characters per document
     for (size_t i = 0; i < n; i++) {
         DocDesc &d = B->docs[i];
         reset_doc(d);
@@ -940,6 +1022,7 @@ dtgpu_status stage_device(dtgpu_decoded *dec, const dtgpu_batch_opts *opts, dtgp
         const DecodeResult &r = Dd.res[i];
         const DecodeDesc &dd = Dd.desc[i];
         const DocFacts f = facts_of(r, prr[i]);
+        n_ins[i] = f.n_ins;
         plan_slots(*B, d, pdesc[i], pres[i], T);
         if (xf) { xf->xf_first[i] = pres[i].xf_first; xf->n_xf[i] = pres[i].n_xf; }
         describe(d, f);
@@ -1025,6 +1108,7 @@ dtgpu_status stage_device(dtgpu_decoded *dec, const dtgpu_batch_opts *opts, dtgp
             B->cut.max_ne = std::max<uint32_t>(B->cut.max_ne, Dd.res[i].n_entries);
         }
         DTGPU_CK(B->d_cutscr.alloc(std::max<uint64_t>(scr, 1)));
+        add_blame_groups(*B, seg_tier, n_ins, T);
     }
     stage_prof("stage: layout + cut plans");
     // every later pass: parent-vector rows as wide as the document's chains (staging counted
@@ -1051,7 +1135,11 @@ dtgpu_status stage_device(dtgpu_decoded *dec, const dtgpu_batch_opts *opts, dtgp
         // without it fails, ErrCheckout site 30)
         mark_critical(*B);
         std::vector<DocDesc> up = B->docs;
-        for (uint32_t d : B->seg_docs) { up[d].seg_lo = 0xFFFFFFFFu; up[d].seg_hi = 0; }
+        for (uint32_t g = 0; g < B->n_cut_groups; g++)
+            for (uint32_t k = 0; k < B->seg_groups[g].count; k++) {
+                DocDesc &e = up[B->seg_docs[B->seg_groups[g].first + k]];
+                e.seg_lo = 0xFFFFFFFFu; e.seg_hi = 0;
+            }
         DTGPU_CK(B->d_docs.upload(up, s));
     }
     if (alloc_arenas(*B, T, Dd.cbyte.p, Dd.content.p) != DTGPU_OK) return DTGPU_ERR_HIP;
@@ -1061,7 +1149,8 @@ dtgpu_status stage_device(dtgpu_decoded *dec, const dtgpu_batch_opts *opts, dtgp
             if (B->ff_doc[i]) ffin.push_back(FFIn{Dd.desc[i].op_off, Dd.res[i].n_ops, uint32_t(i)});
         DTGPU_CK(stage_ff(*B, ffin, Dd.ops.p, Dd.cbyte.p, Dd.content.p, s));
     }
-    if (!B->seg_groups.empty()) {
+    if (stage_blame(*B, T) != DTGPU_OK) return DTGPU_ERR_HIP;
+    if (B->n_cut_groups) {
         DTGPU_CK(B->d_plans.upload(B->seg_plans, s));
         DTGPU_CK(B->d_caps.upload(B->seg_caps, s));
         CutParams &c = B->cut;
@@ -1074,7 +1163,7 @@ dtgpu_status stage_device(dtgpu_decoded *dec, const dtgpu_batch_opts *opts, dtgp
         c.docs = B->d_docs.p;
         c.scr = B->d_cutscr.p;
         c.pent = B->p_pent.p;
-        c.n_groups = uint32_t(B->seg_groups.size());
+        c.n_groups = B->n_cut_groups;
         if (!B->ev_cut) DTGPU_CK(hipEventCreateWithFlags(&B->ev_cut, hipEventDisableTiming));
     }
     if (xf) {   // the transformed-ops replay's arenas, as stage() allocates them for its xf batches

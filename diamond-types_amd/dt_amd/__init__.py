@@ -53,6 +53,13 @@ class BatchOpts(ctypes.Structure):
 
 OPT_NO_FAST_FORWARD, OPT_NO_SEGMENTS, OPT_HOST_PLAN, OPT_NO_SPLIT, OPT_NO_CRITICAL, OPT_DEBUG, OPT_PASS_MARK = \
     1, 2, 4, 8, 16, 32, 64
+OPT_BLAME = 128   # the batch also produces each document's blame on every run (Batch.blame)
+
+
+class BlameRun(ctypes.Structure):
+    """dtgpu_blame_run (include/dtgpu.h): `len` characters of the text, character k inserted by LV
+    lv + k = (agent, seq + k)."""
+    _fields_ = [("lv", ctypes.c_uint32), ("len", ctypes.c_uint32), ("agent", ctypes.c_uint32), ("seq", ctypes.c_uint32)]
 
 
 class GraphQuery(ctypes.Structure):
@@ -244,6 +251,10 @@ def lib():
     L.dtgpu_patches_profile.argtypes = [vp, sz, ctypes.POINTER(ctypes.c_uint32)]
     L.dtgpu_patches_free.argtypes = [vp]
     L.dtgpu_batch_create_decoded.argtypes = [vp, ctypes.POINTER(vp)]
+    L.dtgpu_batch_create_decoded_opts.argtypes = [vp, ctypes.POINTER(BatchOpts), ctypes.POINTER(vp)]
+    L.dtgpu_batch_blame.argtypes = [vp, sz, ctypes.POINTER(BlameRun), sz, ctypes.POINTER(sz)]
+    L.dtgpu_batch_blame_agents.argtypes = [vp, sz, ctypes.c_char_p, sz, ctypes.POINTER(sz)]
+    L.dtgpu_batch_blame_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     psz, pf, psum = ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(Summaries)
     L.dtgpu_oplog_summarize.argtypes = [vp, ctypes.c_char_p, sz, psz, psz, sz, pu64, sz, psz]
     L.dtgpu_oplog_intersect_summary.argtypes = [vp, psum, sz, pu64, sz, psz, pu64, sz, psz]
@@ -832,6 +843,20 @@ class ListOpLog:
         v = self.dominators(version)
         return ListBranch(self.checkout_bytes(v), v)
 
+    def blame(self, version=None):
+        """Who wrote each character of the text at `version` (default: the tip), as
+        Batch.blame_spans gives it: [(agent_name, seq_start, seq_end, char_start, char_end)] in text
+        order.  At a version the history is projected first (history), which renumbers LVs; the
+        (agent name, seq) spans hold across numberings."""
+        if version is not None and not len(version):
+            return []
+        o = self if version is None else self.history(version)
+        b = Batch(oplogs=[o], blame=True)
+        b.run()
+        b.sync()
+        _check(b.results()[0]["status"])
+        return b.blame_spans(0)
+
 
 # dtgpu_export codes (include/dtgpu.h): name -> (code, numpy dtype, fields per record)
 EXPORTS = {
@@ -883,11 +908,14 @@ class Batch:
     (dt_replay.hip) always run on the GPU."""
 
     def __init__(self, docs=None, oplogs=None, ignore_crc=False, host_threads=0, device=0, staging="host",
-                 xf=False, flags=0, seg_ops=0, seg_max=0, lds_fill=0):
+                 xf=False, flags=0, seg_ops=0, seg_max=0, lds_fill=0, blame=False):
         """xf=True (with oplogs): a transformed-ops batch, every document's iter_xf_operations()
         computed by the replay (dtgpu_batch_create_xf); read it with xf_positions(i).  flags
-        (OPT_*), seg_ops, seg_max, lds_fill: dtgpu_batch_opts."""
+        (OPT_*), seg_ops, seg_max, lds_fill: dtgpu_batch_opts.  blame=True (OPT_BLAME; not with
+        xf): every run also leaves each document's blame, read with blame(i) / blame_spans(i)."""
         L = lib()
+        if blame:
+            flags = int(flags) | OPT_BLAME
         opts = BatchOpts(int(ignore_crc), int(host_threads), int(device), int(flags), int(seg_ops), int(seg_max),
                          int(lds_fill))
         out = ctypes.c_void_p()
@@ -968,6 +996,40 @@ class Batch:
 
     def text(self, i) -> bytes:
         return _sized_bytes(lambda *a: lib().dtgpu_batch_text(self._h, i, *a))
+
+    def blame(self, i):
+        """Blame batches: document i's text as maximal runs [(lv, len, agent, seq)] in text order
+        (dtgpu_batch_blame): `len` characters, character k inserted by LV lv + k = (agent, seq + k).
+        A document that failed raises ParseError with its status."""
+        buf, n = _sized(lambda *a: lib().dtgpu_batch_blame(self._h, i, *a), lambda k: (BlameRun * max(1, k))())
+        return [(r.lv, r.len, r.agent, r.seq) for r in buf[:n]]
+
+    def blame_agents(self, i):
+        """The names (bytes) of document i's agent ids, indexed by a run's agent."""
+        return _names(_sized_bytes(lambda *a: lib().dtgpu_batch_blame_agents(self._h, i, *a)))
+
+    def blame_spans(self, i):
+        """blame(i) by name: [(agent_name, seq_start, seq_end, char_start, char_end)], the characters
+        text(i).decode()[char_start:char_end] being (agent_name, seq_start .. seq_end - 1).  Adjacent
+        runs of one agent whose seqs continue are one span even where their LVs do not (LVs are
+        local to an oplog: a merge or a projection numbers them anew), so the spans of a text are
+        the same under every numbering."""
+        names = self.blame_agents(i)
+        out, at = [], 0
+        for _, n, agent, seq in self.blame(i):
+            if out and out[-1][0] == names[agent] and out[-1][2] == seq:
+                out[-1] = out[-1][:2] + (seq + n, out[-1][3], at + n)
+            else:
+                out.append((names[agent], seq, seq + n, at, at + n))
+            at += n
+        return out
+
+    def blame_stats(self):
+        """Of the last run (dtgpu_batch_blame_stats): runs, characters, the blame kernels' us, bytes
+        of the source-list and run arenas."""
+        out = (ctypes.c_uint64 * 4)()
+        _check(lib().dtgpu_batch_blame_stats(self._h, out))
+        return dict(zip(["runs", "chars", "kernel_us", "arena_bytes"], [int(x) for x in out]))
 
     def last_times(self):
         """(plan_ms, replay_ms, prep_ms) of the last run_timed() (prep_ms 0 when host-staged)."""
@@ -1229,15 +1291,43 @@ class DecodeBatch:
         _check(bad)
         return m
 
-    def checkout_batch(self):
+    def checkout_batch(self, blame=False, flags=0, seg_ops=0, seg_max=0, lds_fill=0):
         """A device-staged checkout Batch over these decoded (or merged) oplogs; consumes this
-        handle (dtgpu_batch_create_decoded)."""
+        handle (dtgpu_batch_create_decoded_opts).  blame, flags, seg_ops, seg_max, lds_fill: as
+        Batch takes them."""
         h, self._h = self._h, None
         b = Batch.__new__(Batch)
         out = ctypes.c_void_p()
-        _check(lib().dtgpu_batch_create_decoded(h, ctypes.byref(out)))
+        opts = BatchOpts(0, 0, 0, int(flags) | (OPT_BLAME if blame else 0), int(seg_ops), int(seg_max), int(lds_fill))
+        _check(lib().dtgpu_batch_create_decoded_opts(h, ctypes.byref(opts), ctypes.byref(out)))
         b._h, b.n, b._keep = out.value, self.n, None
         return b
+
+    def blame_versions(self, docs, versions):
+        """Blame at a version for a whole batch: who wrote each character of
+        ListOpLog::checkout(versions[i]) of document docs[i].  As checkout_versions: the histories
+        projected on the GPU (history), then one device-staged blame batch.  Returns (ListBranch,
+        spans) per request, spans as Batch.blame_spans gives them; ROOT requests are (ListBranch(),
+        []).  The projected oplog renumbers LVs, so the runs' LVs are not the base document's: the
+        (agent_name, seq) spans are the answer that holds across numberings.  An output whose
+        projection or checkout fails raises ParseError."""
+        live = [i for i, v in enumerate(versions) if len(v)]
+        out = [(ListBranch(), []) for _ in versions]
+        if not live:
+            return out
+        h = self.history([docs[i] for i in live], [versions[i] for i in live])
+        fronts = []
+        for k in range(len(live)):
+            st, f = h.history_result(k)
+            _check(st)
+            fronts.append(f)
+        b = h.checkout_batch(blame=True)
+        b.run()
+        b.sync()
+        for k, (i, r) in enumerate(zip(live, b.results())):
+            _check(r["status"])
+            out[i] = (ListBranch(b.text(k), fronts[k]), b.blame_spans(k))
+        return out
 
     def profile(self, i):
         out = (ctypes.c_uint32 * 8)()
@@ -1455,6 +1545,18 @@ def batch_checkout(docs, **kw):
     b.sync()
     res = b.results()
     return res, [b.text(i) if r["status"] == 0 else None for i, r in enumerate(res)]
+
+
+def batch_blame(docs, **kw):
+    """Checkout every `.dt` document in `docs` with its blame; returns (results, texts, spans),
+    spans[i] as Batch.blame_spans gives them (None for a document that failed)."""
+    b = Batch(docs=docs, blame=True, **kw)
+    b.run()
+    b.sync()
+    res = b.results()
+    ok = [r["status"] == 0 for r in res]
+    return (res, [b.text(i) if ok[i] else None for i in range(len(res))],
+            [b.blame_spans(i) if ok[i] else None for i in range(len(res))])
 
 
 def device_count() -> int:

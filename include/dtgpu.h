@@ -278,6 +278,7 @@ typedef struct dtgpu_batch_opts {
 #define DTGPU_OPT_NO_CRITICAL 16u      /* no critical-replay priority (DTGPU_CRITICAL=0) */
 #define DTGPU_OPT_DEBUG 32u            /* invariant checks after every replay command (DTGPU_DEBUG=1) */
 #define DTGPU_OPT_PASS_MARK 64u        /* every pass opens with a marker kernel (DTGPU_PASS_MARK) */
+#define DTGPU_OPT_BLAME 128u           /* the batch also produces each document's blame on every run */
 
 typedef struct dtgpu_doc_result {
     uint32_t status;         /* dtgpu_status of this document */
@@ -637,6 +638,33 @@ void dtgpu_merges_free(dtgpu_merges *m);
 /* A device-staged checkout batch over a decoded handle (consumed, also on failure): decoded here
  * unless it already holds merged oplogs; then as dtgpu_batch_create_device. */
 dtgpu_status dtgpu_batch_create_decoded(dtgpu_decoded *dec, dtgpu_batch **out);
+/* The same with options (opts->device is the handle's; NULL: the defaults, as the entry above). */
+dtgpu_status dtgpu_batch_create_decoded_opts(dtgpu_decoded *dec, const dtgpu_batch_opts *opts, dtgpu_batch **out);
+
+/* ---- batched blame: who wrote each character ------------------------------------------------
+ * A batch created with DTGPU_OPT_BLAME (host staging, device staging or a decoded handle, the
+ * results of dtgpu_decode_add and dtgpu_decode_history included; not dtgpu_batch_create_xf:
+ * DTGPU_ERR_ARG) checks out as any other -- the same text, length and hash -- and every run also
+ * leaves each document's blame: the maximal runs (lv, len, agent, seq) in text order.  A run covers
+ * `len` consecutive characters (not bytes) of the text; character k of it was inserted by LV lv + k,
+ * which is (agent, seq + k), agent being the document's agent id as in DTGPU_EXPORT_AGENT_RUNS.
+ * Two adjacent runs never merge: the second's lv is not the first's lv + len, or its agent differs,
+ * or its seq is not the first's seq + len.  The lens add up to the text's length in characters; an
+ * empty text has no runs.  The reference keeps the same information in its tracker and reads it
+ * with lv_span_to_agent_span (src/list/oplog.rs:78) / iter_remote_mappings (:335); it has no blame
+ * call of its own.  The runs are built on the device (dt_blame.hip) and copied back by the first
+ * read after a run, which waits for the batch's stream. */
+typedef struct dtgpu_blame_run { uint32_t lv, len, agent, seq; } dtgpu_blame_run;
+/* Document i's runs, a sized read as dtgpu_batch_text: runs == NULL asks the count in *n;
+ * DTGPU_ERR_ARG when cap is too small, when i is out of range or when the batch was created
+ * without DTGPU_OPT_BLAME.  A document that failed has no runs: *n = 0 and its status is returned. */
+dtgpu_status dtgpu_batch_blame(const dtgpu_batch *b, size_t i, dtgpu_blame_run *runs, size_t cap, size_t *n);
+/* The names of document i's agent ids in the DTGPU_EXPORT_AGENT_NAMES layout (u8 length + bytes,
+ * indexed by dtgpu_blame_run.agent), a sized read in bytes. */
+dtgpu_status dtgpu_batch_blame_agents(const dtgpu_batch *b, size_t i, uint8_t *names, size_t cap, size_t *n);
+/* Of the last run: out[0] = runs, out[1] = characters, out[2] = the blame kernels' time in us,
+ * out[3] = bytes of the source-list and run arenas. */
+dtgpu_status dtgpu_batch_blame_stats(const dtgpu_batch *b, uint64_t out[4]);
 
 /* Decoded-oplog arrays, the same layouts from the device decoder and from a host oplog.
  * Returns the element count (bytes for CONTENT / AGENT_NAMES) and copies min(cap, count). */
